@@ -13,7 +13,13 @@ dtype).  Data: synthetic MNIST-shaped batches resident in HBM.  Every timed
 step does the full work: forward, loss, backward, all-reduce of the 318 KB
 gradient (N > 1) and the SGD apply.
 
-Prints ONE JSON line on rank 0; value = total samples/sec over all N GPUs.
+Prints ONE JSON line on rank 0; value = total samples/sec over all N GPUs,
+ms_per_step = wall time of the K timed steps / K.
+
+A plain run does only what that figure needs (set-up, warm-up, the timed steps).
+``--dump-outputs DIR`` also writes the parameters and loss / accuracy records the
+timed steps left behind as ``DIR/*.npy``; ``--full`` is where any further
+measurement or check goes (none today).
 """
 from __future__ import annotations
 
@@ -106,6 +112,28 @@ def _large_bucket_comm(a, comm, world, rank, dev, max_numel):
     return c
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: everything written stays under this
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``{name: tensor}`` as ``out_dir/<name>.npy`` (float32, or float64 if the tensor
+    is), DUMP_LIMIT_BYTES at most in all.  An array over its share of that limit is cut to a
+    fixed sample: elements of the flattened array at sorted indices drawn with seed 0 (the
+    same elements in every run of the same arguments)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 4096  # (4096: room for the .npy header)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:share // t.element_size()]
+            t = t.reshape(-1)[idx.sort().values.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     if os.environ.get("DTFX_WATCHDOG_S"):  # debugging aid: dump every thread's stack, then exit
         import faulthandler
@@ -154,6 +182,18 @@ def main():
     ap.add_argument("--dataset_size", type=int, default=55000)
     ap.add_argument("--dp", action="store_true",
                     help="use the data-parallel path (gradient all-reduce) even on 1 GPU")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path left its caller "
+                         "after the last step as DIR/<name>.npy (rank 0): the parameters (a "
+                         "fixed seeded sample of them where they exceed 64 MB) and the "
+                         "recorded loss / accuracy.  Same arguments, same inputs: the files of "
+                         "two builds compare array for array")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure.  "
+                         "There is none today: a plain run already does only the set-up, the "
+                         "warm-up, the choice of how the timed steps are issued (--launch "
+                         "auto), the timed steps and the result line; a secondary measurement "
+                         "added later goes behind this option")
     a = ap.parse_args()
     if os.environ.get("DTFX_STACKS_ON_USR1") == "1":  # (diagnostics: all threads' stacks)
         import faulthandler
@@ -344,7 +384,7 @@ def main():
                 med = dict(zip(names, t.cpu().tolist()))
             launch = min(med, key=lambda m: (med[m], m))
             a.launch_probe = {m: round(v, 3) for m, v in med.items()}
-    if launch == "graph":
+    if launch == "graph" and (tr.direct or tr.pending):  # (--warmup 0: no pending update yet)
         tr.prepare(a.steps)
     if launch == "persistent":
         tr.flush()  # the warmup's pending update lands before the clock (it is not a timed step)
@@ -388,6 +428,13 @@ def main():
         identical = bool(same.item())
     ms = elapsed * 1e3 / a.steps
     value = a.batch_size * world * a.steps / elapsed
+    if a.dump_outputs and rank == 0:
+        # what a caller of the trainer holds after the timed steps: the parameters with every
+        # update applied, and the (loss, accuracy) record of the timed steps (those still in
+        # the trainer's ring of records; the last row is the last step's)
+        end = tr.global_step()
+        dump_outputs(a.dump_outputs, {"params": tr.params,
+                                      "loss_acc": tr.stats_range(end - a.steps, end)})
     if rank == 0:
         print(json.dumps({
             "metric": METRIC,
@@ -461,6 +508,9 @@ def bench_bert(a, world, rank, local, dev):
     loss, acc = tr.stats()
     ms = elapsed * 1e3 / a.steps
     seqs = a.bert_batch * world * a.steps / elapsed
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"params": tr.model.params.master,
+                                      "loss_acc": torch.tensor([loss, acc], dtype=torch.float64)})
     if rank == 0:
         print(json.dumps({
             "metric": "sequences/sec (whole node) BERT-%s MLM pre-training, seq %d" % (a.bert_config,
@@ -514,6 +564,9 @@ def bench_resnet(a, world, rank, local, dev):
         elapsed = float(t.item())
     loss, acc = tr.stats()
     ms = elapsed * 1e3 / a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"params": tr.model.params.master,
+                                      "loss_acc": torch.tensor([loss, acc], dtype=torch.float64)})
     if rank == 0:
         print(json.dumps({
             "metric": "images/sec (whole node) ResNet-50 v1.5 training, synthetic ImageNet",
