@@ -31,6 +31,9 @@ void mlp_tf_layout_launch(const float*, float*, int, const float*, int, hipStrea
 void mlp_fwdapply_launch(const float*, float*, float, const float*, const float*, float*, int*,
                          float*, int, int, int, hipStream_t, int);
 void mlp_head2_launch(const float*, const int*, float*, int, hipStream_t, int);
+void mlp_head2_single_launch(const float*, const int*, float*, int, hipStream_t);
+void mlp_rowmajor_layout(int, long long*);
+void wave_reduce_scatter_test_launch(const float*, float*, int, hipStream_t);
 int mlp_single_ks_query();
 int mlp_set_flush_fused(int on);
 void mlp_pipelined_trace_launch(const float*, float*, float, const float*, const float*,
@@ -144,12 +147,29 @@ PYBIND11_MODULE(_hip, m) {
                                      reinterpret_cast<unsigned long long*>(trf),
                                      reinterpret_cast<unsigned long long*>(trh));
   });
-  m.def("mlp_head2", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s, int nslab) {
-    dtfx::mlp_head2_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s), nslab);
+  m.def("mlp_head2", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s, int nslab,
+                        int single) {
+    if (single) {
+      if (nslab != 0) throw std::runtime_error("mlp_head2: single=1 takes nslab=0");
+      dtfx::mlp_head2_single_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s));
+    } else {
+      dtfx::mlp_head2_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s), nslab);
+    }
   }, py::arg("p"), py::arg("labels"), py::arg("ws"), py::arg("B"), py::arg("stream"),
-     py::arg("nslab") = 0,
+     py::arg("nslab") = 0, py::arg("single") = 0,
      "head of the 2-launch step; nslab: slabs the first launch wrote (0: the single-GPU "
-     "step's, 14: every data-parallel engine's)");
+     "step's, 14: every data-parallel engine's); single=1: the single-GPU step's own head, "
+     "which leaves the factors row-major for the next mlp_fwdapply / mlp_apply (the default "
+     "leaves them transposed, as the data-parallel engines read them)");
+  m.def("wave_reduce_scatter_test", [](uintptr_t in, uintptr_t out, int n, uintptr_t s) {
+    dtfx::wave_reduce_scatter_test_launch(P<const float>(in), P<float>(out), n, S(s));
+  }, "one wave: in [64][n] (n = 10 or 16) -> out [64], out[l] = sum over lanes of value l & 15");
+  m.def("mlp_rowmajor_layout", [](int B) {
+    long long o[3];
+    dtfx::mlp_rowmajor_layout(B, o);
+    return py::make_tuple(o[0], o[1], o[2]);
+  }, "(dz1R offset, dlR offset, BP): float offsets of the row-major factor regions dz1R "
+     "[BP][112] and dlR [BP][16] in a workspace of batch B");
   m.def("mlp_run_pipelined", [](uintptr_t p0, uintptr_t p1, int cur, int pending, float lr,
                                 uintptr_t x, uintptr_t lab, int nbatches, int pos, int n,
                                 uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B,

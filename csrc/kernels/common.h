@@ -74,6 +74,73 @@ __device__ __forceinline__ float wave_sum(float v) {
   return a[0];
 }
 
+// Reduce-scatter of N <= 16 values per lane: returns, in EVERY lane l, the sum over all 64
+// lanes of value (l & 15) (garbage where (l & 15) >= N).  Where wave_sum_n carries all N values
+// through every step (8 N VALU ops), this halves the live values at each of the four DPP steps
+// within the 16-lane row -- the lane's bit 3 / 2 / 1 / 0 selects which half of the value
+// indices it keeps, and its partner (row_mirror l ^ 15, row_half_mirror l ^ 7, quad_perm l ^ 2,
+// l ^ 1: all single full-rate DPP moves, and together they reach the whole row) supplies the
+// other lane's partial of the kept half -- and then folds the four rows of the ONE remaining
+// value with the two permlane swaps: 37 ops at N = 10.  A pair (k, k + h) whose upper index is
+// >= N costs one add (the upper half's lanes then carry a value nobody reads).
+// Fixed order: deterministic, the same bits in every run.
+template <int N>
+__device__ __forceinline__ float wave_reduce_scatter(const float (&v)[N], int lane) {
+  static_assert(N >= 1 && N <= 16, "one value index per lane of a 16-lane row");
+  float a[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) a[i] = i < N ? v[i] : 0.f;
+#define DTFX_RS_STEP(HALF, CTRL)                                                       \
+  {                                                                                    \
+    const bool up = (lane & HALF) != 0;                                                \
+    _Pragma("unroll") for (int k = 0; k < HALF; ++k) {                                 \
+      if (k < N) {                                                                     \
+        const float lo = a[k] + dpp_f<CTRL>(a[k]);                                     \
+        if (k + HALF < N) {                                                            \
+          const float hi = a[k + HALF] + dpp_f<CTRL>(a[k + HALF]);                     \
+          a[k] = up ? hi : lo;                                                         \
+        } else {                                                                       \
+          a[k] = lo;                                                                   \
+        }                                                                              \
+      }                                                                                \
+    }                                                                                  \
+  }
+  DTFX_RS_STEP(8, 0x140)  // row_mirror
+  DTFX_RS_STEP(4, 0x141)  // row_half_mirror
+  DTFX_RS_STEP(2, 0x4E)   // quad_perm [2, 3, 0, 1]
+  DTFX_RS_STEP(1, 0xB1)   // quad_perm [1, 0, 3, 2]
+#undef DTFX_RS_STEP
+  float s = a[0];
+  {
+    const int x = __float_as_int(s);
+    auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    s = __int_as_float(r[0]) + __int_as_float(r[1]);
+  }
+  {
+    const int x = __float_as_int(s);
+    auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    s = __int_as_float(r[0]) + __int_as_float(r[1]);
+  }
+  return s;
+}
+
+// Sum / max over the 16-lane row of every lane (quad_perm xor 1 / xor 2, row_ror 4 / 8: every
+// lane of the row ends with the result).
+__device__ __forceinline__ float row_sum16(float v) {
+  v += dpp_f<0xB1>(v);
+  v += dpp_f<0x4E>(v);
+  v += dpp_f<0x124>(v);
+  v += dpp_f<0x128>(v);
+  return v;
+}
+__device__ __forceinline__ float row_max16(float v) {
+  v = fmaxf(v, dpp_f<0xB1>(v));
+  v = fmaxf(v, dpp_f<0x4E>(v));
+  v = fmaxf(v, dpp_f<0x124>(v));
+  v = fmaxf(v, dpp_f<0x128>(v));
+  return v;
+}
+
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 // tanh(u) = 1 - 2 / (1 + e^{2u}): one v_exp_f32 + one v_rcp_f32 (libm tanhf is a long

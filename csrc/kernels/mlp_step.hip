@@ -16,9 +16,17 @@
 //                h = sigmoid, logits = h . W2 + b2, softmax, xent, accuracy,
 //                dlogits = (p - y)/B, dz1 = (dlogits . W2^T) * h * (1 - h)
 //                -> hbuf [b][j], dz1T [j][b], dlT [c][b], rowstat [b]
+//                (head of the single-GPU two-launch step, RM: the factors go out
+//                 ROW-major instead, dz1R [b][j] as one 8-B store per lane -- a
+//                 coalesced 400-B run per row -- and dlR [b][16]; nothing is
+//                 stored to dz1T / dlT then)
 //   K3 mlp_wgrad 343 blocks: dW1^T tile = dz1^T . x   (f32 MFMA, K = batch)
 //                  7 blocks: dW2^T = dl^T . h, db1, db2 (MFMA against ones),
 //                            mean loss / accuracy -> stats ring
+//                (the single-GPU two-launch step's first launch, mlp_fwdapply
+//                 <.., XW = 0, KS3>, reads dz1R / dlR: its W1 update runs over
+//                 quads of 4 batch rows, one dz1R value and one float2 of x per
+//                 lane and quad)
 //                direct mode: the SGD apply is fused into the epilogue
 //                (each parameter element is owned by exactly one lane);
 //                grad mode: writes the flat gradient for an all-reduce.
@@ -92,6 +100,11 @@ struct Bufs {            // workspace (zero-initialised once; padding stays 0)
   float* rowstat;        // [BP][2]       per-row (loss, correct)
   int* sync;             // [4] handoff words of mlp_head_flush_kernel (0 between launches):
                          //     [0] head rows done, [1] apply blocks done, [2] sticky timeout
+  // the single-GPU two-launch step's factors, row-major: regions of their own AFTER the sync
+  // words (StepWorkspace.buf ends at sync + 4: FusedMLPTrainer.check() and the tests' views
+  // size that part; the allocation, mlp_workspace_floats, goes on)
+  float* dz1R;           // [BP][HP]      dz1 row-major
+  float* dlR;            // [BP][16]      dlogits row-major
 };
 
 __device__ __forceinline__ float4 f4(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -243,13 +256,16 @@ __device__ __forceinline__ void head_allgather(const MlpXg& xg, unsigned ep, int
 // factors that mlp_wgrad_factor_kernel turns into the global weight gradient.
 // (the body of one row's wave: mlp_head_kernel runs it as a one-wave block, the terminal
 // head + apply kernel of a launched region as one of four waves of a block)
-template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS>
+// RM: the factors are stored row-major (dz1R / dlR) for mlp_fwdapply_kernel<.., 0, .., KS3>
+// and NOT to dz1T / dlT.
+template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false>
 __device__ __forceinline__ void head_row(
     const int row, const int lane, const float* __restrict__ p_old,
     const float* __restrict__ grad, float lr, float* __restrict__ p_new,
     const int* __restrict__ labels, const Bufs& w, int B, unsigned long long* __restrict__ tr,
     const MlpXg& xg, float* __restrict__ dz1A) {
   static_assert(XW == 0 || (!APPLY && !TRACE), "the factor exchange runs the direct step");
+  static_assert(!RM || (XW == 0 && !APPLY), "row-major factors: the single-GPU two-launch step");
   if (TRACE) trace_stamp(tr, row * 4 + 0);
   const int BP = ((B + 15) >> 4) * 16;
   const int y = labels[row];
@@ -261,7 +277,7 @@ __device__ __forceinline__ void head_row(
   // z1 slabs, b1, the 10 W2 columns -- arrives as one 8-B load per pair: 49 load
   // instructions per lane instead of 88 (more than the 63 a wave can keep in flight:
   // the 28-slab step waited out a second round trip here).
-  float hv[2], w2[2][C], zs[2], b1v[2], b2v[C];
+  float hv[2], w2[2][C], zs[2], b1v[2];
   int jj[2];
   bool jv[2];
   const int j0 = min(2 * lane, H - 2);  // (H even: j0, j0 + 1 always a valid, aligned pair)
@@ -288,9 +304,12 @@ __device__ __forceinline__ void head_row(
     w2[0][c] = v.x;
     w2[1][c] = v.y;
   }
-#pragma unroll
-  for (int c = 0; c < C; ++c) b2v[c] = p_old[OFF_B2 + c];
-  float gb1[2], gw2[2][C], gb2[C];
+  // class-per-lane part of the row: lane l works on class cl = l & 15 (live: cl < C; all four
+  // 16-lane rows carry the same values)
+  const int cl = lane & 15, cc = min(cl, C - 1);
+  const bool clive = cl < C;
+  float b2l = p_old[OFF_B2 + cc];
+  float gb1[2], gw2[2][C], gb2l = 0.f;
   if (APPLY) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -298,8 +317,7 @@ __device__ __forceinline__ void head_row(
 #pragma unroll
       for (int c = 0; c < C; ++c) gw2[u][c] = grad[OFF_W2 + c * H + jj[u]];
     }
-#pragma unroll
-    for (int c = 0; c < C; ++c) gb2[c] = grad[OFF_B2 + c];
+    gb2l = grad[OFF_B2 + cc];
   }
   __builtin_amdgcn_sched_barrier(0);  // all loads in flight together
   if (APPLY) {
@@ -309,8 +327,7 @@ __device__ __forceinline__ void head_row(
 #pragma unroll
       for (int c = 0; c < C; ++c) w2[u][c] -= lr * gw2[u][c];
     }
-#pragma unroll
-    for (int c = 0; c < C; ++c) b2v[c] -= lr * gb2[c];
+    b2l -= lr * gb2l;
     if (publish) {
 #pragma unroll
       for (int u = 0; u < 2; ++u)
@@ -319,12 +336,7 @@ __device__ __forceinline__ void head_row(
 #pragma unroll
           for (int c = 0; c < C; ++c) p_new[OFF_W2 + c * H + jj[u]] = w2[u][c];
         }
-      if (lane < C) {
-        float b2l = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) b2l = (lane == c) ? b2v[c] : b2l;
-        p_new[OFF_B2 + lane] = b2l;
-      }
+      if (lane < C) p_new[OFF_B2 + lane] = b2l;
     }
   }
   if (TRACE) trace_stamp(tr, row * 4 + 1);
@@ -335,29 +347,30 @@ __device__ __forceinline__ void head_row(
     for (int c = 0; c < C; ++c) w2[u][c] = jv[u] ? w2[u][c] : 0.f;
     if (jv[u]) w.hbuf[(size_t)row * HP + jj[u]] = hv[u];
   }
-  // logits = h . W2 + b2 (10 interleaved DPP wave reductions; every lane ends with all 10)
-  float lg[C];
+  // logits = h . W2 + b2: a reduce-scatter leaves class cl's logit on lane l, and the softmax
+  // runs ONE class per lane -- one v_exp_f32 per lane, 16-lane row reductions for the max and
+  // the denominator -- where all 64 lanes used to repeat the 10-class chains on the same ten
+  // numbers (~400 VALU issues of the one wave, the head's compute span)
+  float lgp[C];
 #pragma unroll
-  for (int c = 0; c < C; ++c) lg[c] = hv[0] * w2[0][c] + hv[1] * w2[1][c];
-  wave_sum_n(lg);
-#pragma unroll
-  for (int c = 0; c < C; ++c) lg[c] += b2v[c];
-
-  float m = lg[0];
-  int am = 0;
-#pragma unroll
-  for (int c = 1; c < C; ++c)
-    if (lg[c] > m) { m = lg[c]; am = c; }  // first max, like tf.argmax
-  float se = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) se += __expf(lg[c] - m);
+  for (int c = 0; c < C; ++c) lgp[c] = hv[0] * w2[0][c] + hv[1] * w2[1][c];
+  const float lgc = wave_reduce_scatter(lgp, lane) + b2l;
+  const float m = row_max16(clive ? lgc : -INFINITY);
+  // first max, like tf.argmax: the lowest class whose logit equals the max
+  const unsigned long long atmax = __ballot(lane < C && lgc == m);
+  const int am = atmax ? __builtin_ctzll(atmax) : 0;
+  const float ec = clive ? __expf(lgc - m) : 0.f;
+  const float se = row_sum16(ec);
   const float inv = fast_rcp(se), invB = 1.f / (float)B;
-  float dl[C], ly = 0.f;
+  const int yu = __builtin_amdgcn_readfirstlane(y);  // (wave-uniform: the row's label)
+  const float mydl = (ec * inv - (cl == yu ? 1.f : 0.f)) * invB;  // dlogits of class cl
+  const float ly = (unsigned)yu < (unsigned)C  // the label's logit (0 for a label out of range)
+                       ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(lgc), yu & 15))
+                       : 0.f;
+  float dl[C];
 #pragma unroll
-  for (int c = 0; c < C; ++c) {
-    dl[c] = (__expf(lg[c] - m) * inv - (c == y ? 1.f : 0.f)) * invB;
-    ly = (c == y) ? lg[c] : ly;
-  }
+  for (int c = 0; c < C; ++c)
+    dl[c] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mydl), c));
   float dzv[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
@@ -368,9 +381,12 @@ __device__ __forceinline__ void head_row(
 #pragma unroll
       for (int c = 0; c < C; ++c) dh += dl[c] * w2[u][c];
       dzv[u] = dh * hv[u] * (1.f - hv[u]);
-      w.dz1T[(size_t)j * BP + row] = dzv[u];
+      if (!RM) w.dz1T[(size_t)j * BP + row] = dzv[u];
     }
   }
+  if (RM && lane < H / 2)
+    *reinterpret_cast<float2*>(&w.dz1R[(size_t)row * HP + 2 * lane]) =
+        make_float2(dzv[0], dzv[1]);
   if constexpr (XW > 0) {
     bool fail = false;
     if (xg.split & 16) head_allgather<XW, true>(xg, ep, row, lane, BP, dzv, dz1A, fail);
@@ -379,10 +395,10 @@ __device__ __forceinline__ void head_row(
     if (fail) atomicExch(xg.err, 1);
   }
   if (TRACE) trace_stamp(tr, row * 4 + 2);
-  float mydl = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) mydl = (lane == c) ? dl[c] : mydl;
-  if (lane < C) w.dlT[(size_t)lane * BP + row] = mydl;
+  if (lane < C) {
+    if (RM) w.dlR[(size_t)row * 16 + lane] = mydl;
+    else w.dlT[(size_t)lane * BP + row] = mydl;
+  }
   if (lane == 0) {
     w.rowstat[2 * row] = m + __logf(se) - ly;  // xent of this row
     w.rowstat[2 * row + 1] = (am == y) ? 1.f : 0.f;
@@ -390,12 +406,12 @@ __device__ __forceinline__ void head_row(
   if (TRACE) trace_stamp(tr, row * 4 + 3);
 }
 
-template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS>
+template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false>
 __global__ __launch_bounds__(64) void mlp_head_kernel(
     const float* __restrict__ p_old, const float* __restrict__ grad, float lr,
     float* __restrict__ p_new, const int* __restrict__ labels, Bufs w, int B,
     unsigned long long* __restrict__ tr, MlpXg xg, float* __restrict__ dz1A) {
-  head_row<APPLY, TRACE, XW, NSLAB>(blockIdx.x, threadIdx.x, p_old, grad, lr, p_new, labels, w,
+  head_row<APPLY, TRACE, XW, NSLAB, RM>(blockIdx.x, threadIdx.x, p_old, grad, lr, p_new, labels, w,
                                      B, tr, xg, dz1A);
 }
 
@@ -669,7 +685,9 @@ __device__ __forceinline__ void xg_exchange2(const MlpXg& xg, unsigned ep, const
 // p_src: where the current parameter values are read (== p except in the pipelined step,
 // which reads the old ping-pong buffer and writes the new one); stats_on = 0 skips the
 // loss/accuracy record and the global_step increment.
-template <bool DIRECT, int NGT, int XW>
+// RM: the factors are read from the row-major regions dz1R / dlR (one value per lane and batch
+// row; the same (group, element) -> row order of the K sum as the transposed form's float4).
+template <bool DIRECT, int NGT, int XW, bool RM = false>
 __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx,
                                             float* __restrict__ p, float lr,
                                             float* __restrict__ grad, const Bufs& w,
@@ -725,7 +743,17 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   float bv[MAXG][4];
 #pragma unroll
   for (int g = 0; g < MAXG; ++g)
-    if (g < NG) av[g] = f4(A + g * 16);
+    if (g < NG) {
+      if constexpr (RM) {
+        const float* AR = (role == 1) ? w.dz1R + jt * 16 + r : w.dlR + r;
+        const int pitch = (role == 1) ? HP : 16;
+        const int b = g * 16 + q * 4;
+        av[g] = float4{AR[(size_t)b * pitch], AR[(size_t)(b + 1) * pitch],
+                       AR[(size_t)(b + 2) * pitch], AR[(size_t)(b + 3) * pitch]};
+      } else {
+        av[g] = f4(A + g * 16);
+      }
+    }
   if (dw2) {  // one uniform branch around the whole B-operand load block
 #pragma unroll
     for (int g = 0; g < MAXG; ++g)
@@ -952,6 +980,10 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(
 // instead of 28 + 16..32.  f32 MFMAs issue at 32 cycles each on one SIMD, so with one wave
 // per SIMD the MFMA issue itself set the two phases' length (profiles/r3/mlp_trace/pmc.md:
 // 41 % of the waves' cycles were issue stalls).
+// XW == 0 with KSX = KS3 (the single-GPU step): the factors are ROW-major (dz1R / dlR, written
+// by head_row<.., RM>) and phase A runs in row-quad form instead -- wave w takes a quarter of
+// the batch's quads of 4 rows for all 28 features, the four partials are added in wave order
+// through LDS and waves 0 / 1 apply one accumulator each (profiles/rowmajor_factors/).
 // FWD = false (mlp_apply_launch: the pending update of the last pipelined step, the flush):
 // phase A and the small parameters only -- no forward, no x loads.
 // (the body of block `bid`: mlp_fwdapply_kernel runs it with bid = blockIdx.x, the terminal
@@ -979,16 +1011,19 @@ __device__ __forceinline__ void fwdapply_block(
   constexpr int KSP = 4 / NCG;             // phase-A K splits (waves per column group)
   constexpr int G2 = (KWX + 15) / 16;      // phase-B 16-feature groups
   static_assert(KSX * KWX == D && KWX % 4 == 0 && NCG * KSP == 4, "K slicing");
+  // the single-GPU step's factors are row-major (head_row<.., RM>): phase A in row-quad form
+  constexpr bool RM = XW == 0 && KSX == KS3;
   if (bid >= HT * KSX) {
     const int jt = bid - HT * KSX;
-    wgrad_small<true, NGT, XW>(jt, wave, lane, MLP_XG_SMALL_EPOCH + jt * 4 + wave, p_new, lr,
+    wgrad_small<true, NGT, XW, RM>(jt, wave, lane, MLP_XG_SMALL_EPOCH + jt * 4 + wave, p_new, lr,
                                nullptr, w, ctr, stats, stats_ring, B, xg, p_old, stats_on);
     if (TRACE) trace_stamp(trw, 3);
     return;
   }
   constexpr int LW = KWX + 4;  // LDS row pitch (floats)
   __shared__ float Wt[16][LW];
-  __shared__ float Kred[KSP > 1 ? NCG : 1][64][4];  // phase-A K-split partials
+  __shared__ float Kred[!RM && KSP > 1 ? NCG : 1][64][4];  // phase-A K-split partials
+  __shared__ f32x4 red[RM ? 4 * 2 * 64 : 1];               // row-quad form: (wave, accumulator)
   const int jt = bid / KSX, ks = bid % KSX;
   const int f0 = ks * KWX;
   // phase B's x rows are independent of phase A: requested first, so the whole launch
@@ -1008,8 +1043,71 @@ __device__ __forceinline__ void fwdapply_block(
     }
   }
 
-  // ---- phase A: this wave's 16 x 16 slice of the updated W1 tile (K split sp of KSP) -----
-  {
+  if constexpr (RM) {
+    // ---- phase A, row-quad form (after fx_phase_a_quads): wave w covers ALL 28 features of
+    // the slice for its quarter of the batch's row quads (NG each).  Per quad of 4 rows a lane
+    // loads ONE dz1R value (hidden r of row base + q: a 64-B run per row) and ONE float2 of x
+    // (features 2r, 2r + 1; lanes r >= 14 are dead) and feeds two MFMAs (accumulator e:
+    // features 2r + e): at 112 rows 14 operand loads and 14 MFMAs per wave where the
+    // column-group form has 20 and 16, and the slice is not padded to 32 features.  Rows >= B
+    // read a clamped x row and a zero factor.  The four partials are added in wave order
+    // through LDS; wave e in {0, 1} applies accumulator e.
+    const bool lv = r < KWX / 2;
+    const int fo = 2 * (lv ? r : KWX / 2 - 1);
+    float pw[4] = {0.f, 0.f, 0.f, 0.f};
+    if (wave < 2) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = jt * 16 + q * 4 + i;
+        pw[i] = p_old[OFF_W1 + (size_t)(j < H ? j : H - 1) * D + f0 + fo + wave];
+      }
+    }
+    float av[MAXG];
+    float2 xv[MAXG];
+    const int u0 = wave * NG;
+#pragma unroll
+    for (int u = 0; u < MAXG; ++u) {
+      if (u < NG) {
+        const int row = (u0 + u) * 4 + q;  // < 16 NG = BP
+        av[u] = w.dz1R[(size_t)row * HP + jt * 16 + r];
+        xv[u] = *reinterpret_cast<const float2*>(x_prev + (size_t)(row < B ? row : B - 1) * D +
+                                                 f0 + fo);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // all loads in flight together
+    if (TRACE) trace_stamp(trw, 1);
+    f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+#pragma unroll
+    for (int u = 0; u < MAXG; ++u) {
+      if (u < NG) {
+        a0 = mfma16x16x4(av[u], xv[u].x, a0);
+        a1 = mfma16x16x4(av[u], xv[u].y, a1);
+      }
+    }
+    red[(wave * 2 + 0) * 64 + lane] = a0;
+    red[(wave * 2 + 1) * 64 + lane] = a1;
+    __syncthreads();
+    if (wave < 2) {
+      f32x4 part = red[wave * 64 + lane];
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {  // wave order
+        const f32x4 o = red[(k * 2 + wave) * 64 + lane];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) part[i] += o[i];
+      }
+      const int fl = fo + wave;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int hl = q * 4 + i, j = jt * 16 + hl;
+        const float v = pw[i] - lr * part[i];
+        if (lv) {
+          if (FWD) Wt[hl][fl] = j < H ? v : 0.f;  // padded hidden rows contribute exact zeros
+          if (j < H) p_new[OFF_W1 + (size_t)j * D + f0 + fl] = v;
+        }
+      }
+    }
+  } else {
+    // ---- phase A: this wave's 16 x 16 slice of the updated W1 tile (K split sp of KSP) -----
     const int cgp = wave % NCG, sp = wave / NCG;
     const int fl = cgp * 16 + r;            // feature within the block's slice
     const bool cv = fl < KWX;               // (14 slices: wave 3 has 8 live columns)
@@ -1243,8 +1341,9 @@ __global__ __launch_bounds__(256) void mlp_head_flush_kernel(
   if (bid < nhb) {
     const int row = bid * 4 + wave;
     if (row >= B) return;
-    head_row<false, false, 0, KSX>(row, lane, p_cur, p_cur, 0.f, nullptr, labels, w, B, nullptr,
-                                   MlpXg{}, nullptr);
+    // (KS3: row-major factors, what its apply blocks' fwdapply_block<.., 0, .., KS3> reads)
+    head_row<false, false, 0, KSX, KSX == KS3>(row, lane, p_cur, p_cur, 0.f, nullptr, labels, w, B,
+                                               nullptr, MlpXg{}, nullptr);
     // release at agent scope: the wave's stores are complete and written back past this
     // XCD's L2 before the count moves (one add per row)
     if (lane == 0) __hip_atomic_fetch_add(w.sync, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -1636,6 +1735,8 @@ static mlp::Bufs make_bufs(float* ws, int B) {
   b.dlT = b.dz1T + (size_t)HP * BP;
   b.rowstat = b.dlT + (size_t)16 * BP;
   b.sync = reinterpret_cast<int*>(b.rowstat + (size_t)2 * BP);
+  b.dz1R = b.rowstat + (size_t)2 * BP + 4;
+  b.dlR = b.dz1R + (size_t)BP * HP;
   return b;
 }
 
@@ -1697,11 +1798,48 @@ void mlp_tf_layout_launch(const float* src, float* dst, int to_tf, const float* 
 long long mlp_workspace_floats(int B) {
   using namespace mlp;
   const long long BP = ((B + 15) / 16) * 16;
-  return (long long)NSLAB_MAX * BP * HP + BP * HP + HP * BP + 16 * BP + 2 * BP + 4;
+  return (long long)NSLAB_MAX * BP * HP + BP * HP + HP * BP + 16 * BP + 2 * BP + 4 + BP * HP +
+         16 * BP;
 }
 
+// Float offsets of the row-major factor regions in a workspace of batch B: out = {dz1R, dlR,
+// BP}.  The sync words are the 4 floats before dz1R (where StepWorkspace.buf ends).
 static void check_b(int B) {
   if (B < 1 || B > mlp::MAXB) throw std::runtime_error("fused MLP step: batch must be in [1, 256]");
+}
+
+// Test kernel of wave_reduce_scatter (common.h): one wave, in [64][N] -> out [64]
+// (out[l] = the value lane l holds: the sum over all lanes of value l & 15).
+template <int N>
+__global__ __launch_bounds__(64) void wave_reduce_scatter_test_kernel(
+    const float* __restrict__ in, float* __restrict__ out) {
+  const int lane = threadIdx.x;
+  float v[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = in[lane * N + i];
+  out[lane] = wave_reduce_scatter(v, lane);
+}
+
+void wave_reduce_scatter_test_launch(const float* in, float* out, int n, hipStream_t stream) {
+  if (n == 10)
+    hipLaunchKernelGGL((wave_reduce_scatter_test_kernel<10>), dim3(1), dim3(64), 0, stream, in, out);
+  else if (n == 16)
+    hipLaunchKernelGGL((wave_reduce_scatter_test_kernel<16>), dim3(1), dim3(64), 0, stream, in, out);
+  else
+    throw std::runtime_error("wave_reduce_scatter_test: n must be 10 or 16");
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+void mlp_rowmajor_layout(int B, long long* out) {
+  check_b(B);
+  float* const base = reinterpret_cast<float*>(uintptr_t(1) << 32);  // (never dereferenced)
+  const mlp::Bufs b = make_bufs(base, B);
+  out[0] = b.dz1R - base;
+  out[1] = b.dlR - base;
+  out[2] = ((B + 15) / 16) * 16;
+  if (reinterpret_cast<float*>(b.sync) + 4 != b.dz1R ||
+      b.dlR + 16 * out[2] - base != mlp_workspace_floats(B))
+    throw std::runtime_error("mlp_rowmajor_layout: workspace size out of step with its layout");
 }
 
 // K1: grad != nullptr => deferred apply (p_new must differ from p_old)
@@ -2042,8 +2180,8 @@ void mlp_pipelined_trace_launch(const float* p_old, float* p_new, float lr, cons
     hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, true, false, KS3>), dim3(HT * KS3 + HT), dim3(256),
                        0, stream, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, 1,
                        MlpXg{}, trf);
-    hipLaunchKernelGGL((mlp_head_kernel<false, true, 0, KS3>), dim3(B), dim3(64), 0, stream, p_new,
-                       p_new, 0.f, nullptr, labels, w, B, trh, MlpXg{}, nullptr);
+    hipLaunchKernelGGL((mlp_head_kernel<false, true, 0, KS3, true>), dim3(B), dim3(64), 0, stream,
+                       p_new, p_new, 0.f, nullptr, labels, w, B, trh, MlpXg{}, nullptr);
   } else {
     hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, true>), dim3(HT * KS2 + HT), dim3(256), 0, stream,
                        p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, 1, MlpXg{}, trf);
@@ -2068,6 +2206,21 @@ void mlp_head2_launch(const float* p, const int* labels, float* ws, int B, hipSt
   else
     hipLaunchKernelGGL((mlp_head_kernel<false, false, 0, KS2>), dim3(B), dim3(64), 0, stream, p, p,
                        0.f, nullptr, labels, w, B, nullptr, MlpXg{}, nullptr);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// Head of the single-GPU two-launch step: after mlp_fwdapply_launch's 28-slice form it leaves
+// the factors ROW-major (dz1R / dlR), which the next step's first launch and the flush
+// (mlp_apply_launch) read; with DTFX_MLP_KS=14 the step keeps the transposed layout.  (The
+// data-parallel engines' heads -- mlp_head2_launch with their nslab -- stay transposed.)
+void mlp_head2_single_launch(const float* p, const int* labels, float* ws, int B,
+                             hipStream_t stream) {
+  using namespace mlp;
+  if (mlp_single_ks() != KS3) return mlp_head2_launch(p, labels, ws, B, stream, KS2);
+  check_b(B);
+  const Bufs w = make_bufs(ws, B);
+  hipLaunchKernelGGL((mlp_head_kernel<false, false, 0, KS3, true>), dim3(B), dim3(64), 0, stream,
+                     p, p, 0.f, nullptr, labels, w, B, nullptr, MlpXg{}, nullptr);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2162,9 +2315,9 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
         hipLaunchKernelGGL((mlp_fwdapply_kernel<0, 0, false, false, KS3>), dim3(HT * KS3 + HT),
                            dim3(256), 0, stream, po, pn, l, xprev, xcur, w, ctr, stats, stats_ring,
                            B, pending, MlpXg{}, nullptr);
-      hipLaunchKernelGGL((mlp_head_kernel<false, false, 0, KS3>), dim3(B), dim3(64), 0, stream, pn,
-                         pn, 0.f, nullptr, labels + (size_t)pos * B, w, B, nullptr, MlpXg{},
-                         nullptr);
+      hipLaunchKernelGGL((mlp_head_kernel<false, false, 0, KS3, true>), dim3(B), dim3(64), 0,
+                         stream, pn, pn, 0.f, nullptr, labels + (size_t)pos * B, w, B, nullptr,
+                         MlpXg{}, nullptr);
     } else {
       if (rt7)
         hipLaunchKernelGGL((mlp_fwdapply_kernel<7>), dim3(HT * KS2 + HT), dim3(256), 0, stream, po,

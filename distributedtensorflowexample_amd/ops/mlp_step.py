@@ -86,11 +86,22 @@ class StepWorkspace:
         self.B = B
         self.device = torch.device(device)
         n = hip().mlp_workspace_floats(B) if self.device.type == "cuda" else 1
-        self.buf = torch.zeros(int(n), device=device, dtype=torch.float32)
+        self.store = torch.zeros(int(n), device=device, dtype=torch.float32)
+        # ``buf``: the workspace up to and including its 4 hand-off words (``buf[-4:]``); the
+        # row-major factor regions of the single-GPU two-launch step (dz1R [BP][112], dlR
+        # [BP][16]: ``rowmajor_factors()``) follow it in the same allocation
+        self._rm = hip().mlp_rowmajor_layout(B) if self.device.type == "cuda" else (int(n), 0, 0)
+        self.buf = self.store[:self._rm[0]]
         # global_step (advanced on the device by mlp_wgrad)
         self.ctr = torch.zeros(1, device=device, dtype=torch.int32)
         self.stats_ring = stats_ring
         self.stats = torch.zeros(stats_ring, 2, device=device, dtype=torch.float32)
+
+    def rowmajor_factors(self):
+        """Views (dz1R [BP, 112], dlR [BP, 16]) of the row-major factor regions."""
+        o_dz, o_dl, BP = self._rm
+        return (self.store[o_dz:o_dz + BP * HP].view(BP, HP),
+                self.store[o_dl:o_dl + BP * 16].view(BP, 16))
 
     def global_step(self) -> int:
         return int(self.ctr[0].item())
@@ -132,7 +143,9 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     (from the factors dz1/h/dlogits the last head left in ``ws`` and the previous batch
     ``x_prev``; W1 never materialises a gradient) reading ``p_old`` and writing ``p_new``,
     and runs this step's forward on the updated W1; ``mlp_head2`` (28 partial z1 slabs:
-    the single-GPU K slicing, ``hip().mlp_single_ks()``) finishes the step.  ``apply=False`` (nothing pending): a plain copy + forward.  The
+    the single-GPU K slicing, ``hip().mlp_single_ks()``; ``single=1``: it leaves dz1 / dlogits
+    row-major, as the next ``mlp_fwdapply`` / ``mlp_apply`` reads them) finishes the step.
+    ``apply=False`` (nothing pending): a plain copy + forward.  The
     last step's update stays pending until ``flush_pipelined``."""
     _check(x, labels, ws.B)
     _check(x_prev, None, ws.B)
@@ -143,7 +156,7 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     h.mlp_fwdapply(ptr(p_old), ptr(p_new), float(lr) if apply else 0.0,
                    ptr(x_prev if apply else x), ptr(x), ptr(ws.buf), ptr(ws.ctr),
                    ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, 1 if apply else 0, s)
-    h.mlp_head2(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s)
+    h.mlp_head2(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s, 0, 1)  # (row-major factors)
 
 
 def flush_pipelined(p_old, p_new, x_prev, ws: StepWorkspace, lr, stats=True):

@@ -65,7 +65,7 @@ def main():
     def single():
         h.mlp_fwdapply(ptr(p[0]), ptr(p[1]), 1e-4, ptr(xp), ptr(xc), ptr(ws.buf), ptr(ws.ctr),
                        ptr(ws.stats), ws.stats_ring, B, 1, stream_handle())
-        h.mlp_head2(ptr(p[1]), ptr(yc), ptr(ws.buf), B, stream_handle())
+        h.mlp_head2(ptr(p[1]), ptr(yc), ptr(ws.buf), B, stream_handle(), 0, 1)
 
     out["single_gpu_2launch_us"] = round(graph_us(single, dev), 2)
     engines = [e for e in os.environ.get("ENGINES", "fused2,fused2x,factor2,fused,factor").split(",") if e]

@@ -57,7 +57,7 @@ def main():
         if traced is None:
             h.mlp_fwdapply(ptr(p[cur]), ptr(p[cur ^ 1]), lr, ptr(xp), ptr(xb), ptr(ws.buf),
                            ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, B, 1, s)
-            h.mlp_head2(ptr(p[cur ^ 1]), ptr(yb), ptr(ws.buf), B, s)
+            h.mlp_head2(ptr(p[cur ^ 1]), ptr(yb), ptr(ws.buf), B, s, 0, 1)
         else:
             h.mlp_pipelined_trace(ptr(p[cur]), ptr(p[cur ^ 1]), lr, ptr(xp), ptr(xb), ptr(yb),
                                   ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, B, s,
