@@ -67,6 +67,8 @@ void philox_init_launch(long long, float*, unsigned long long, unsigned long lon
                         float, hipStream_t);
 void act_bwd_launch(long long, int, const float*, const float*, float*, hipStream_t);
 void act_fwd_launch(long long, int, const float*, float*, hipStream_t);
+void shuffle_rows_launch(float*, const float*, int*, const int*, long long, int, long long,
+                         long long, unsigned, unsigned, hipStream_t);
 }  // namespace dtfx
 
 void register_rccl(py::module_& m);
@@ -283,6 +285,17 @@ PYBIND11_MODULE(_hip, m) {
   m.def("act_fwd", [](long long n, int act, uintptr_t x, uintptr_t y, uintptr_t s) {
     dtfx::act_fwd_launch(n, act, P<const float>(x), P<float>(y), S(s));
   });
+  m.def("shuffle_rows", [](uintptr_t dst, uintptr_t src, uintptr_t dst_lab, uintptr_t src_lab,
+                           long long n, int planes, long long dst_stride, long long src_stride,
+                           unsigned seed, unsigned epoch, uintptr_t s) {
+    dtfx::shuffle_rows_launch(P<float>(dst), P<const float>(src), P<int>(dst_lab),
+                              P<const int>(src_lab), n, planes, dst_stride, src_stride, seed, epoch,
+                              S(s));
+  }, py::arg("dst"), py::arg("src"), py::arg("dst_labels"), py::arg("src_labels"), py::arg("n"),
+     py::arg("planes"), py::arg("dst_stride"), py::arg("src_stride"), py::arg("seed"),
+     py::arg("epoch"), py::arg("stream"),
+     "per-epoch reshuffle gather: dst[w][j] = src[w][perm(seed, epoch, n)[j]] over `planes` "
+     "planes of [n, 784] f32 (strides in floats) and the int32 labels (csrc/kernels/shuffle.hip)");
   m.def("calib", [](int mode, int grid, int block, uintptr_t ctr, uintptr_t data, uintptr_t out,
                     uintptr_t s) {
     dtfx::calib_launch(mode, grid, block, P<const int>(ctr), P<const float>(data), P<float>(out),

@@ -226,6 +226,11 @@ def define_reference_flags(flag_values=FLAGS):
                    "than --num_workers makes the slowest workers backups)", fv)
     DEFINE_boolean("zero1", False, "Autograd sync-DP path: shard the optimizer update over the "
                    "replicas (ZeRO-1: reduce-scatter, owner update, all-gather)", fv)
+    DEFINE_boolean("shuffle", False, "--strategy mirrored: reshuffle each replica's resident "
+                   "training shard at every epoch boundary, the first epoch included (like the "
+                   "reference's next_batch); the order is a pure function of (--shuffle_seed, "
+                   "epoch), so a restored run continues in it", fv)
+    DEFINE_integer("shuffle_seed", 0, "--shuffle: seed of the per-epoch permutation", fv)
     DEFINE_float("dist_timeout_secs", 300.0,
                  "Sync DP: timeout of the gloo control-plane collectives (torch's default is "
                  "30 min); a rank whose peer died raises after at most this long", fv)

@@ -29,7 +29,23 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   all-gather only the backprop factors dz1 (40 KB) inside ``mlp_head`` and
   each forms the global W1 gradient itself (sufficient-factor exchange);
 * ``global_step`` is a device counter advanced by the kernels (AssignAdd of
-  worker.py:32,141); loss/accuracy land in a device ring read back lazily.
+  worker.py:32,141); loss/accuracy land in a device ring read back lazily;
+* ``shuffle=True`` reshuffles the resident dataset at every epoch boundary, the
+  first epoch included, like the reference's ``next_batch`` (worker.py:133).
+  Nothing joins the step: the order is changed BETWEEN epochs.  The pristine
+  dataset stays resident next to two shuffled buffers; epoch ``e = global_step
+  // nbatches`` reads buffer ``e & 1``, whose position j holds original row
+  ``ops.shuffle.shuffle_index(shuffle_seed, e, n)[j]`` (a pure function: a run
+  resumed with ``seek(global_step)`` and every data-parallel rank reproduce it;
+  with ``factor_comm`` every rank's plane of ``x_all`` is shuffled locally).
+  The gather for epoch e + 1 (``csrc/kernels/shuffle.hip``) is launched in order
+  on the compute stream when the position wraps, between two graph replays;
+  the step kernels keep reading plain contiguous batches.  All n rows are
+  permuted and the first ``nbatches * B`` positions are fed, so the dropped tail
+  differs every epoch.  The update pending across a boundary reads the previous
+  epoch's last batch from the OTHER buffer -- hence two; the C++ host loops,
+  which wrap inside one base pointer, are called once per epoch, and the
+  persistent launch, which wraps inside the kernel, is refused.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -50,7 +66,8 @@ from ..ops._ext import stream_handle
 class FusedMLPTrainer:
     def __init__(self, params, x, labels, batch_size=100, learning_rate=0.001, allreduce=None,
                  world_size=1, stats_ring=4096, global_step=0, max_graph_steps=1024,
-                 fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True):
+                 fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
+                 shuffle=False, shuffle_seed=0):
         if not params.is_cuda:
             raise ValueError("FusedMLPTrainer runs on the GPU; use the generic path on CPU")
         if params.numel() != mlp_step.NPARAM:
@@ -84,6 +101,9 @@ class FusedMLPTrainer:
         if self.nbatches < 1:
             raise ValueError("dataset smaller than one batch")
         self.x, self.labels = x, labels
+        self.shuffle = bool(shuffle)
+        self.shuffle_seed = int(shuffle_seed)
+        self.epoch = 0  # epoch of the next step (advanced in shuffle mode only)
         self.bufs = [params.detach().clone().contiguous(), torch.empty_like(params)]
         self.cur = 0
         self.grad = torch.zeros_like(params)
@@ -104,6 +124,21 @@ class FusedMLPTrainer:
         self._ebase = 0   # epoch base of its next launch
         self._unchecked = False  # a persistent launch whose hand-offs were not verified yet
         self._host_args = None   # run_launched's cached launcher and buffer addresses
+        if self.shuffle:
+            # the pristine dataset (x0 / labels0, with factor_comm the whole x_all) plus TWO
+            # shuffled buffers: epoch e reads buffer e & 1, and the update pending across the
+            # boundary still reads epoch e - 1's last batch from the other one.  ``x`` /
+            # ``labels`` / ``_host_args`` always name the CURRENT epoch's buffer (``_bind``).
+            self.x0, self.labels0 = x, labels
+            src = x_all if factor_comm is not None else x
+            self._src = src
+            self._dst = [torch.empty_like(src), torch.empty_like(src)]
+            self.xs = [d[int(rank)] if factor_comm is not None else d for d in self._dst]
+            self.ys = [torch.empty_like(labels), torch.empty_like(labels)]
+            self._hargs = [None, None]
+            self.run_launched = self._run_launched_epochs
+            self._bind(int(global_step) // self.nbatches)
+            self._gather()
 
     # -- state --------------------------------------------------------------
     @property
@@ -132,16 +167,16 @@ class FusedMLPTrainer:
         self._verified()
         if self.pending:
             if self.pipelined and self.factor_comm is not None:
-                xp, _ = self.batch((self.pos - 1) % self.nbatches)
+                xp = self._xprev(self.pos)
                 mlp_step.flush_factor(self.bufs[self.cur], xp, self.ws, self.lr / self.world_size,
                                       self.factor_comm, self.dz1A, self.xstride)
             elif self.pipelined and self.fused_comm is not None:
-                xp, _ = self.batch((self.pos - 1) % self.nbatches)
+                xp = self._xprev(self.pos)
                 mlp_step.flush_xgmi(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, self.ws,
                                     self.lr / self.world_size, self.fused_comm)
                 self.cur ^= 1
             elif self.pipelined:
-                xp, _ = self.batch((self.pos - 1) % self.nbatches)
+                xp = self._xprev(self.pos)
                 mlp_step.flush_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, self.ws,
                                          self.lr)
                 self.cur ^= 1
@@ -183,12 +218,61 @@ class FusedMLPTrainer:
         sl = slice(i * self.B, (i + 1) * self.B)
         return self.x[sl], self.labels[sl]
 
+    def _xprev(self, pos):
+        """The batch before position ``pos`` of the stream: the pending update's input.  In
+        shuffle mode the batch before position 0 is the LAST batch of the previous epoch, which
+        lives in the other shuffled buffer."""
+        i = (pos - 1) % self.nbatches
+        x = self.xs[(self.epoch - 1) & 1] if (self.shuffle and pos == 0) else self.x
+        return x[i * self.B:(i + 1) * self.B]
+
+    # -- per-epoch reshuffle (shuffle=True) ------------------------------------
+    def _bind(self, epoch):
+        """Point ``x`` / ``labels`` / the host loop's cached addresses at ``epoch``'s buffer
+        (host mirrors only: nothing is launched)."""
+        self._hargs[self.epoch & 1] = self._host_args
+        self.epoch = int(epoch)
+        k = self.epoch & 1
+        self.x, self.labels, self._host_args = self.xs[k], self.ys[k], self._hargs[k]
+
+    def _gather(self):
+        """Write the current epoch's order into its buffer: position j <- original row
+        ``shuffle_index(shuffle_seed, epoch, n)[j]`` (every plane of x_all with factor_comm),
+        in order on the compute stream."""
+        from ..ops.shuffle import shuffle_rows_
+
+        k = self.epoch & 1
+        shuffle_rows_(self._dst[k], self.ys[k], self._src, self.labels0, self.shuffle_seed,
+                      self.epoch)
+
+    def _wrapped(self):
+        """After the step(s) that moved ``pos``: at an epoch boundary in shuffle mode, move to
+        the next epoch's buffer and fill it.  The buffer it overwrites held epoch e - 1, whose
+        last reader (the first step of epoch e) was launched before."""
+        if self.shuffle and self.pos == 0:
+            self._bind(self.epoch + 1)
+            self._gather()
+
+    def seek(self, global_step):
+        """Position the trainer at ``global_step``: the device counter, the batch position and
+        (shuffle mode) the epoch, whose buffer is regenerated -- a resumed run continues in the
+        order an uninterrupted one has.  A pending update is applied first; nothing is pending
+        afterwards."""
+        self.flush()
+        s = int(global_step)
+        self.ws.set_global_step(s)
+        self.pos = s % self.nbatches
+        if self.shuffle:
+            self._bind(s // self.nbatches)
+            self._gather()
+
     # -- one step (eager) -----------------------------------------------------
     def _step_launches(self):
         xb, yb = self.batch(self.pos)
+        p0 = self.pos
         self.pos = (self.pos + 1) % self.nbatches
         if self.factor_comm is not None and self.pipelined:
-            xp, _ = self.batch((self.pos - 2) % self.nbatches)  # pos already advanced
+            xp = self._xprev(p0)
             mlp_step.step_factor_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb,
                                            yb, self.ws, self.lr / self.world_size, self.pending,
                                            self.factor_comm, self.dz1A, self.xstride)
@@ -200,7 +284,7 @@ class FusedMLPTrainer:
                                  self.factor_comm, self.dz1A, self.xstride)
             return
         if self.fused_comm is not None and self.pipelined:
-            xp, _ = self.batch((self.pos - 2) % self.nbatches)  # pos already advanced
+            xp = self._xprev(p0)
             mlp_step.step_xgmi_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb,
                                          yb, self.ws, self.lr / self.world_size, self.pending,
                                          self.fused_comm)
@@ -215,7 +299,7 @@ class FusedMLPTrainer:
             mlp_step.step_direct(self.bufs[self.cur], xb, yb, self.ws, self.lr)
             return
         if self.pipelined:
-            xp, _ = self.batch((self.pos - 2) % self.nbatches)  # pos already advanced
+            xp = self._xprev(p0)
             mlp_step.step_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
                                     self.ws, self.lr, apply=self.pending)
             self.cur ^= 1
@@ -234,6 +318,7 @@ class FusedMLPTrainer:
 
     def step(self):
         self._step_launches()
+        self._wrapped()
 
     # -- hipGraph capture/replay ---------------------------------------------
     def _graph(self, n):
@@ -243,7 +328,7 @@ class FusedMLPTrainer:
         position, ping-pong parity, pending flag) move during capture; they are
         restored afterwards and advanced by the caller at replay.
         """
-        key = (n, self.pos, self.cur)
+        key = (n, self.pos, self.cur, self.epoch & 1)  # (the x pointers: the shuffle buffer)
         g = self._graphs.get(key)
         if g is None:
             pos, cur, pend = self.pos, self.cur, self.pending
@@ -327,6 +412,29 @@ class FusedMLPTrainer:
         self.cur ^= (steps + (1 if flush else 0)) & 1
         self.pending = not flush
 
+    def _run_launched_epochs(self, steps, flush=False):
+        """``run_launched`` of a shuffle-mode trainer (bound over it in ``__init__``, so the
+        shuffle-free call stays exactly as it is: a driver-sized timed region pays its Python
+        side before the first kernel).  The C++ host loops take ONE base pointer and wrap
+        inside it, so they are called once per epoch with that epoch's buffer; the step right
+        after a boundary, whose pending update reads the previous epoch's last batch from the
+        other buffer, is issued with explicit pointers.  A ``flush`` that ends an epoch runs
+        inside the C++ call (its x_prev is that epoch's own last batch)."""
+        steps = int(steps)
+        if not self.host_loop_ok:
+            raise RuntimeError("run_launched: pipelined single-GPU step or exchange engine only")
+        while steps > 0:
+            if self.pos == 0 and self.pending:
+                self.step()
+                steps -= 1
+                continue
+            n = min(steps, self.nbatches - self.pos)
+            FusedMLPTrainer.run_launched(self, n, flush and n == steps)
+            self._wrapped()
+            steps -= n
+        if flush:
+            self.flush()
+
     def _run_launched_engine(self, steps, flush):
         """run_launched for the pipelined exchange engines: every rank issues the same steps
         from one C++ call (the in-kernel exchanges pair them up across ranks)."""
@@ -354,8 +462,10 @@ class FusedMLPTrainer:
     # -- persistent single-launch engine (csrc/kernels/mlp_persistent.hip) ----------------
     @property
     def persistent_ok(self):
-        """The plain single-GPU step with batch <= 128 can run as ONE persistent launch."""
-        return self.host_loop_ok and self.world_size == 1 and self.B <= 128
+        """The plain single-GPU step with batch <= 128 can run as ONE persistent launch (not in
+        shuffle mode: that launch wraps around one dataset buffer inside the kernel)."""
+        return (self.host_loop_ok and self.world_size == 1 and self.B <= 128
+                and not self.shuffle)
 
     def run_persistent(self, steps, timeout_s=2.0, trace=None):
         """``steps`` complete SGD steps (every update applied, nothing left pending) in ONE
@@ -368,7 +478,8 @@ class FusedMLPTrainer:
 
         steps = int(steps)
         if not self.persistent_ok:
-            raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only")
+            raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
+                               "(and shuffle off)")
         if steps <= 0:
             return
         self.flush()  # a pending pipelined update is applied first (params exact)
@@ -408,29 +519,33 @@ class FusedMLPTrainer:
         steps = int(steps)
         if not use_graph:
             for _ in range(steps):
-                self._step_launches()
+                self.step()
             return
         if lead > 0 and self.host_loop_ok:
             k = min(int(lead), steps)
             self.run_launched(k)
             steps -= k
         if steps > 0 and not self.direct and not self.pending:
-            self._step_launches()  # the first DP step has nothing to apply
+            self.step()  # the first DP step has nothing to apply
             steps -= 1
         for n in self._plan(steps):
             self._graph(n).replay()
             self.pos = (self.pos + n) % self.nbatches
             if not self.direct:
                 self.cur ^= n & 1
+            if self.shuffle and self.pos == 0:  # the next epoch's gather, between two replays
+                self._wrapped()
 
     def prepare(self, steps, lead=0):
         """Capture (not run) every graph a following ``run(steps, lead=lead)`` replays."""
         steps = int(steps)
         if steps > 0 and not self.direct and not self.pending:
             raise RuntimeError("prepare() in DP mode needs one eager step first")
-        pos, cur = self.pos, self.cur
+        pos, cur, epoch = self.pos, self.cur, self.epoch
         if lead > 0 and self.host_loop_ok:
             k = min(int(lead), steps)
+            if self.shuffle:
+                self._bind(self.epoch + (self.pos + k) // self.nbatches)
             self.pos = (self.pos + k) % self.nbatches
             self.cur ^= k & 1
             steps -= k
@@ -439,7 +554,11 @@ class FusedMLPTrainer:
             self.pos = (self.pos + n) % self.nbatches
             if not self.direct:
                 self.cur ^= n & 1
+            if self.shuffle and self.pos == 0:
+                self._bind(self.epoch + 1)  # (host mirrors only: which buffer the graph reads)
         self.pos, self.cur = pos, cur
+        if self.shuffle:
+            self._bind(epoch)
 
     # -- observability ------------------------------------------------------
     def stats(self, step=None):

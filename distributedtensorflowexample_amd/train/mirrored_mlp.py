@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from ..models import mlp as mlp_model
 from ..ops import mlp_step, nn, optim
+from ..ops.shuffle import shuffle_index
 from ..parallel.comm import NativeComm, TorchComm
 from ..parallel.watchdog import init_process_group_with_timeout, maybe_inject_fault, watch_peers
 from ..optim import GradientDescentOptimizer
@@ -88,6 +89,10 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     is_chief = rank == 0
     steps_total = int(flags.training_steps if max_steps is None else max_steps)
     B = int(flags.batch_size)
+    # --shuffle: every replica's shard in a new order each epoch (ops/shuffle.py: a pure
+    # function of seed and epoch, the same on the GPU engines and the autograd path)
+    shuffle = bool(getattr(flags, "shuffle", False))
+    shuffle_seed = int(getattr(flags, "shuffle_seed", 0) or 0)
 
     params = mlp_model.init_params(dev, seed=int(flags.seed))  # identical on every rank
     # each replica trains on its own shard of the (shuffled) training set
@@ -125,7 +130,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              allreduce=comm.allreduce_sum_ if (comm and not (fused or factor))
                              else None, world_size=world, fused_comm=fused, factor_comm=factor,
                              x_all=x_all if factor is not None else None, rank=rank,
-                             pipeline=pipe if comm is not None else True)
+                             pipeline=pipe if comm is not None else True,
+                             shuffle=shuffle, shuffle_seed=shuffle_seed)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -145,7 +151,15 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         def step_fn():
             i = state["pos"]
             n = tr_x.shape[0] // B
-            xb, yb = tr_x[(i % n) * B:(i % n + 1) * B], tr_y[(i % n) * B:(i % n + 1) * B]
+            if shuffle:  # position j of epoch e holds original row shuffle_index(seed, e, rows)[j]
+                e = i // n
+                if state.get("epoch") != e:
+                    state["epoch"], state["perm"] = e, shuffle_index(shuffle_seed, e,
+                                                                     tr_x.shape[0])
+                idx = state["perm"][(i % n) * B:(i % n + 1) * B]
+                xb, yb = tr_x[idx], tr_y[idx]
+            else:
+                xb, yb = tr_x[(i % n) * B:(i % n + 1) * B], tr_y[(i % n) * B:(i % n + 1) * B]
             state["pos"] = i + 1
             if ddp:
                 ddp.reset()
@@ -185,8 +199,7 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         tf_vars_to_flat(values, p)
         if use_gpu:
             tr.load_params(p.to(dev))
-            tr.ws.set_global_step(int(values["global/global_step"]))
-            tr.pos = int(values["global/global_step"]) % tr.nbatches
+            tr.seek(int(values["global/global_step"]))
         else:
             model.flat.data.copy_(p)
             state["pos"] = int(values["global/global_step"])
@@ -228,8 +241,7 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             s = int(s.item())
             if use_gpu:
                 tr.load_params(p)
-                tr.ws.set_global_step(s)
-                tr.pos = s % tr.nbatches
+                tr.seek(s)
             else:
                 model.flat.data.copy_(p)
                 state["pos"] = s
