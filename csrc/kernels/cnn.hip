@@ -1064,6 +1064,13 @@ void sgd_momentum_mixed_launch(long long n, float* p, const float* g, float* v, 
   if (n % 4) throw std::runtime_error("sgd_momentum_mixed: n % 4 != 0");
   if (nseg < 0 || nseg > kSgdMaxSegs || (nseg && !segs))
     throw std::runtime_error("sgd_momentum_mixed: 0..128 segments with a table");
+  // float4 accesses of p, g, v (and the table's int64 rows), 8-byte bf16x4 stores to pb: a
+  // bucket slice of the flat buffers that starts off these boundaries is rejected here
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
+       reinterpret_cast<uintptr_t>(v)) & 15)
+    throw std::runtime_error("sgd_momentum_mixed: p, g, v must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(pb) | reinterpret_cast<uintptr_t>(segs)) & 7)
+    throw std::runtime_error("sgd_momentum_mixed: pb and segs must be 8-byte aligned");
   if (nseg) {
     hipLaunchKernelGGL(sgd_momentum_mixed_segs_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, n,
                        p, g, v, (unsigned short*)pb, lr, mu, wd, gscale, segs, nseg);

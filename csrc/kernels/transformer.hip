@@ -1536,6 +1536,9 @@ __global__ __launch_bounds__(256) void adam_mixed_kernel(
   const int t = step_ptr ? *step_ptr : step;
   const float bc1 = 1.f - powf(b1, (float)t), bc2 = 1.f - powf(b2, (float)t);
   const float step_size = lr / bc1, rbc2 = rsqrtf(bc2);
+  // p -= lr * wd * p as the one fma the compiler contracted it to; a zero decay (frozen
+  // parameters: lr = 0) leaves p alone bit for bit, where -0 - 0 * -0 would give +0
+  const float decay = lr * wd;
   const long long n4 = n >> 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -1546,7 +1549,7 @@ __global__ __launch_bounds__(256) void adam_mixed_kernel(
       const float gg = gv[u] * gscale;
       mv[u] = b1 * mv[u] + (1.f - b1) * gg;
       vv[u] = b2 * vv[u] + (1.f - b2) * gg * gg;
-      pv[u] -= lr * wd * pv[u];
+      pv[u] = decay == 0.f ? pv[u] : __builtin_fmaf(-decay, pv[u], pv[u]);
       pv[u] -= step_size * mv[u] / (sqrtf(vv[u]) * rbc2 + eps);
       o[u] = (short)tobf(pv[u]);
     }
@@ -1586,6 +1589,9 @@ __global__ __launch_bounds__(256) void adam_mixed_segs_kernel(
   const int t = step_ptr ? *step_ptr : step;
   const float bc1 = 1.f - powf(b1, (float)t), bc2 = 1.f - powf(b2, (float)t);
   const float step_size = lr / bc1, rbc2 = rsqrtf(bc2);
+  // p -= lr * wd * p as the one fma the compiler contracted it to; a zero decay (frozen
+  // parameters: lr = 0) leaves p alone bit for bit, where -0 - 0 * -0 would give +0
+  const float decay = lr * wd;
   const long long n4 = n >> 2;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
@@ -1635,7 +1641,7 @@ __global__ __launch_bounds__(256) void adam_mixed_segs_kernel(
       const float gg = gv[u] * gscale;
       mv[u] = b1 * mv[u] + (1.f - b1) * gg;
       vv[u] = b2 * vv[u] + (1.f - b2) * gg * gg;
-      pv[u] -= lr * wd * pv[u];
+      pv[u] = decay == 0.f ? pv[u] : __builtin_fmaf(-decay, pv[u], pv[u]);
       pv[u] -= step_size * mv[u] / (sqrtf(vv[u]) * rbc2 + eps);
       o[u] = (short)tobf(pv[u]);
     }
@@ -2181,6 +2187,13 @@ void adam_mixed_launch(long long n, float* p, const float* g, float* m, float* v
   if (n <= 0) return;
   if (nseg < 0 || nseg > kAdamMaxSegs || (nseg && !segs))
     throw std::runtime_error("adam_mixed: 0..128 segments with a table");
+  // float4 accesses of p, g, m, v (and the table's int64 rows), 8-byte bf16x4 stores to pb: a
+  // bucket slice of the flat buffers that starts off these boundaries is rejected here
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
+       reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15)
+    throw std::runtime_error("adam_mixed: p, g, m, v must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(pb) | reinterpret_cast<uintptr_t>(segs)) & 7)
+    throw std::runtime_error("adam_mixed: pb and segs must be 8-byte aligned");
   long long blocks = (n / 4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (nseg) {

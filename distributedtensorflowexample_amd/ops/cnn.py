@@ -766,7 +766,13 @@ def avgpool_bwd(dy, x_shape):
 def sgd_momentum_mixed(p, g, v, pb, lr, momentum=0.9, wd=0.0, gscale=1.0, segs=None):
     """Momentum SGD on the f32 master (bf16 copy refreshed).  ``segs`` (GPU): int64 [n][5]
     table of ranges whose gradient is the sum of split-K planes (see conv_wgrad ``planes``)."""
-    if segs is not None and p.is_cuda:
+    if segs is not None and not p.is_cuda:
+        raise ValueError("sgd_momentum_mixed: segments are a GPU path")
+    if segs is not None:
+        if not (segs.is_cuda and segs.dtype == torch.int64 and segs.is_contiguous()
+                and segs.dim() == 2 and segs.shape[1] == 5):
+            raise ValueError("sgd_momentum_mixed: segs must be a contiguous int64 [nseg, 5] "
+                             "GPU tensor")
         hip().sgd_momentum_mixed(p.numel(), ptr(p), ptr(g), ptr(v), ptr(pb), float(lr),
                                  float(momentum), float(wd), float(gscale), stream_handle(),
                                  segs=ptr(segs), nseg=int(segs.shape[0]))
