@@ -38,7 +38,10 @@ int mlp_single_ks_query();
 int mlp_set_flush_fused(int on);
 void mlp_pipelined_trace_launch(const float*, float*, float, const float*, const float*,
                                 const int*, float*, int*, float*, int, int, hipStream_t,
-                                unsigned long long*, unsigned long long*);
+                                unsigned long long*, unsigned long long*, unsigned long long*);
+void mlp_lean_fwdapply_launch(const float*, float*, float, const float*, const float*, float*, int*,
+                              float*, int, int, int, hipStream_t);
+void mlp_lean_head_launch(const float*, const int*, float*, int, hipStream_t);
 void mlp_run_pipelined_launch(float*, float*, int, int, float, const float*, const int*, int, int,
                               int, float*, int*, float*, int, int, hipStream_t, int);
 void mlp_apply_launch(const float*, float*, float, const float*, float*, int*, float*, int, int,
@@ -142,13 +145,35 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mlp_pipelined_trace", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
                                    uintptr_t x, uintptr_t lab, uintptr_t ws, uintptr_t ctr,
                                    uintptr_t stats, int ring, int B, uintptr_t s, uintptr_t trf,
-                                   uintptr_t trh) {
+                                   uintptr_t trh, uintptr_t trs) {
     dtfx::mlp_pipelined_trace_launch(P<const float>(p_old), P<float>(p_new), lr,
                                      P<const float>(x_prev), P<const float>(x), P<const int>(lab),
                                      P<float>(ws), P<int>(ctr), P<float>(stats), ring, B, S(s),
                                      reinterpret_cast<unsigned long long*>(trf),
-                                     reinterpret_cast<unsigned long long*>(trh));
-  });
+                                     reinterpret_cast<unsigned long long*>(trh),
+                                     reinterpret_cast<unsigned long long*>(trs));
+  }, py::arg("p_old"), py::arg("p_new"), py::arg("lr"), py::arg("x_prev"), py::arg("x"),
+     py::arg("labels"), py::arg("ws"), py::arg("ctr"), py::arg("stats"), py::arg("ring"),
+     py::arg("B"), py::arg("stream"), py::arg("trf"), py::arg("trh"), py::arg("trs") = 0,
+     "one traced two-launch step; trs (optional, 28 slices): [(7 * 28 + 7) * 4][2] split stamps "
+     "of the first launch (slot 0: its first-issued operand class has landed)");
+  m.def("mlp_lean_fwdapply", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                                uintptr_t x, uintptr_t ws, uintptr_t ctr, uintptr_t stats,
+                                int ring, int B, int stats_on, uintptr_t s) {
+    dtfx::mlp_lean_fwdapply_launch(P<const float>(p_old), P<float>(p_new), lr,
+                                   P<const float>(x_prev), P<const float>(x), P<float>(ws),
+                                   P<int>(ctr), P<float>(stats), ring, B, stats_on, S(s));
+  }, py::arg("p_old"), py::arg("p_new"), py::arg("lr"), py::arg("x_prev"), py::arg("x"),
+     py::arg("ws"), py::arg("ctr"), py::arg("stats"), py::arg("ring"), py::arg("B"),
+     py::arg("stats_on"), py::arg("stream"),
+     "first launch of the single-GPU two-launch step: the lean kernel (packed, preloaded kernel "
+     "arguments; the same results as mlp_fwdapply(ks=28)); with DTFX_MLP_KS=14 the 14-slice "
+     "mlp_fwdapply");
+  m.def("mlp_lean_head", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s) {
+    dtfx::mlp_lean_head_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s));
+  }, py::arg("p"), py::arg("labels"), py::arg("ws"), py::arg("B"), py::arg("stream"),
+     "head of the single-GPU two-launch step after mlp_lean_fwdapply: row-major factors out, as "
+     "mlp_head2(single=1)");
   m.def("mlp_head2", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s, int nslab,
                         int single) {
     if (single) {

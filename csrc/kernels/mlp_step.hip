@@ -31,6 +31,16 @@
 //                (each parameter element is owned by exactly one lane);
 //                grad mode: writes the flat gradient for an all-reduce.
 //
+// The single-GPU two-launch step (bench.py's default workload) runs through LEAN entry points,
+// mlp_lean_fwdapply_kernel / mlp_lean_head_kernel: the fwdapply_block<.., 0, .., KS3> /
+// head_row<.., RM> bodies behind kernel arguments of scalars and pointers only (at most 16
+// dwords; the workspace regions derived from one base pointer through ws_layout), preloaded
+// into user SGPRs at wave launch, and with phase A's own operands (dz1R / x_prev, then W1)
+// requested before phase B's cold x rows, so the first MFMA does not wait for those
+// (profiles/lean_step/: -0.56 us per step, bit-identical results).  mlp_fwdapply_launch /
+// mlp_head2_launch, the data-parallel engines and the opt-in fused flush keep
+// mlp_fwdapply_kernel / mlp_head_kernel.  Measured and not kept there: tile-major z1 slabs.
+//
 // All MFMA work is v_mfma_f32_16x16x4_f32 (exact f32).  Lane l supplies
 // A[i = l&15][k = l>>4], B[k = l>>4][j = l&15]; C[row = (l>>4)*4 + r][col = l&15].
 // A float4 load of k = 16g + 4q .. 16g + 4q + 3 feeds 4 MFMAs (element e is
@@ -107,7 +117,50 @@ struct Bufs {            // workspace (zero-initialised once; padding stays 0)
   float* dlR;            // [BP][16]      dlogits row-major
 };
 
+// Float offsets of the workspace regions for a padded batch of BP rows: the ONE definition the
+// host launchers (make_bufs, mlp_workspace_floats) and the lean step's kernels (which take the
+// workspace base pointer alone) share.
+struct WsLayout {
+  long long hbuf, dz1T, dlT, rowstat, sync, dz1R, dlR, total;
+};
+__host__ __device__ constexpr WsLayout ws_layout(long long BP) {
+  WsLayout o{};
+  o.hbuf = (long long)NSLAB_MAX * BP * HP;
+  o.dz1T = o.hbuf + BP * HP;
+  o.dlT = o.dz1T + HP * BP;
+  o.rowstat = o.dlT + 16 * BP;
+  o.sync = o.rowstat + 2 * BP;
+  o.dz1R = o.sync + 4;
+  o.dlR = o.dz1R + BP * HP;
+  o.total = o.dlR + 16 * BP;
+  return o;
+}
+__host__ __device__ __forceinline__ Bufs ws_bufs(float* ws, int BP) {
+  const WsLayout o = ws_layout(BP);
+  Bufs b;
+  b.slab = ws;
+  b.hbuf = ws + o.hbuf;
+  b.dz1T = ws + o.dz1T;
+  b.dlT = ws + o.dlT;
+  b.rowstat = ws + o.rowstat;
+  b.sync = reinterpret_cast<int*>(ws + o.sync);
+  b.dz1R = ws + o.dz1R;
+  b.dlR = ws + o.dlR;
+  return b;
+}
+
 __device__ __forceinline__ float4 f4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// trace_stamp (common.h) that leaves the wave's N most recent vector memory operations in
+// flight: vector loads return in order, so it marks "everything but the last N has landed".
+template <int N>
+__device__ __forceinline__ void trace_stamp_vm(unsigned long long* tr, int slot) {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+  const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if ((threadIdx.x & 63) == 0) tr[slot] = t;
+}
 
 // ---------------------------------------------------------------------------
 // K1: partial z1 over one K slice (+ deferred W1 apply)
@@ -258,7 +311,8 @@ __device__ __forceinline__ void head_allgather(const MlpXg& xg, unsigned ep, int
 // head + apply kernel of a launched region as one of four waves of a block)
 // RM: the factors are stored row-major (dz1R / dlR) for mlp_fwdapply_kernel<.., 0, .., KS3>
 // and NOT to dz1T / dlT.
-template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false>
+// NGT > 0: the batch is padded to NGT * 16 rows at compile time.
+template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false, int NGT = 0>
 __device__ __forceinline__ void head_row(
     const int row, const int lane, const float* __restrict__ p_old,
     const float* __restrict__ grad, float lr, float* __restrict__ p_new,
@@ -267,7 +321,7 @@ __device__ __forceinline__ void head_row(
   static_assert(XW == 0 || (!APPLY && !TRACE), "the factor exchange runs the direct step");
   static_assert(!RM || (XW == 0 && !APPLY), "row-major factors: the single-GPU two-launch step");
   if (TRACE) trace_stamp(tr, row * 4 + 0);
-  const int BP = ((B + 15) >> 4) * 16;
+  const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
   const int y = labels[row];
   const unsigned ep = XW > 0 ? xg.epochs[MLP_XG_HEAD_EPOCH + row] + 1 : 0u;
   const bool publish = APPLY && row == 0;
@@ -988,12 +1042,20 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(
 // phase A and the small parameters only -- no forward, no x loads.
 // (the body of block `bid`: mlp_fwdapply_kernel runs it with bid = blockIdx.x, the terminal
 // head + apply kernel of a launched region with FWD = false on its apply blocks)
-template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true>
+// ORD (the lean step, row-quad form): phase A's own operands are requested FIRST -- dz1R / x_prev,
+// then the W1 values pw, then phase B's rows xa.  Vector loads return in order, so the first
+// MFMA's vmcnt then leaves pw and the cold xa rows in flight instead of waiting for them.
+// trs (TRACE, NGT > 0, optional): [blocks * 4 waves][2] split stamps -- 0: the first-issued operand
+// class has landed (ORD: factors + x_prev; else the xa rows), 1: unused.
+template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true,
+          bool ORD = false>
 __device__ __forceinline__ void fwdapply_block(
     const int bid, const float* __restrict__ p_old, float* __restrict__ p_new, float lr,
     const float* __restrict__ x_prev, const float* __restrict__ x, const Bufs& w,
     int* __restrict__ ctr, float* __restrict__ stats, int stats_ring, int B, int stats_on,
-    const MlpXg& xg, unsigned long long* __restrict__ tr) {
+    const MlpXg& xg, unsigned long long* __restrict__ tr,
+    unsigned long long* __restrict__ trs = nullptr) {
+  static_assert(!ORD || (XW == 0 && KSX == KS3), "load order of the row-quad form");
   // stamps per wave: 0 entry, 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab
   // stored; with XW > 0 also 4 local gradient slice ready (exchange starts), 5 two-shot: the
   // owned sums done (first hop), 6 exchange done -- 8 slots per wave then
@@ -1031,17 +1093,20 @@ __device__ __forceinline__ void fwdapply_block(
   constexpr int RTW = 2;
   float4 xa[RTW][G2];
   float rmv[RTW];
+  auto load_xa = [&]() {
 #pragma unroll
-  for (int t = 0; t < (FWD ? RTW : 0); ++t) {
-    const int row = (wave + 4 * t) * 16 + r;
-    const float* xr = x + (size_t)(row < B ? row : B - 1) * D + f0;
-    rmv[t] = row < B ? 1.f : 0.f;
+    for (int t = 0; t < (FWD ? RTW : 0); ++t) {
+      const int row = (wave + 4 * t) * 16 + r;
+      const float* xr = x + (size_t)(row < B ? row : B - 1) * D + f0;
+      rmv[t] = row < B ? 1.f : 0.f;
 #pragma unroll
-    for (int g = 0; g < G2; ++g) {
-      const int k = 16 * g + 4 * q;
-      xa[t][g] = f4(xr + (k < KWX ? k : 0));
+      for (int g = 0; g < G2; ++g) {
+        const int k = 16 * g + 4 * q;
+        xa[t][g] = f4(xr + (k < KWX ? k : 0));
+      }
     }
-  }
+  };
+  if constexpr (!ORD) load_xa();
 
   if constexpr (RM) {
     // ---- phase A, row-quad form (after fx_phase_a_quads): wave w covers ALL 28 features of
@@ -1055,13 +1120,18 @@ __device__ __forceinline__ void fwdapply_block(
     const bool lv = r < KWX / 2;
     const int fo = 2 * (lv ? r : KWX / 2 - 1);
     float pw[4] = {0.f, 0.f, 0.f, 0.f};
-    if (wave < 2) {
+    // (the wave-uniform branch also keeps the loads HERE: issued unconditionally, the compiler
+    // sinks them into the apply branch after the barrier -- a serial round trip)
+    auto load_pw = [&]() {
+      if (wave < 2) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int j = jt * 16 + q * 4 + i;
-        pw[i] = p_old[OFF_W1 + (size_t)(j < H ? j : H - 1) * D + f0 + fo + wave];
+        for (int i = 0; i < 4; ++i) {
+          const int j = jt * 16 + q * 4 + i;
+          pw[i] = p_old[OFF_W1 + (size_t)(j < H ? j : H - 1) * D + f0 + fo + wave];
+        }
       }
-    }
+    };
+    if constexpr (!ORD) load_pw();
     float av[MAXG];
     float2 xv[MAXG];
     const int u0 = wave * NG;
@@ -1074,7 +1144,21 @@ __device__ __forceinline__ void fwdapply_block(
                                                  f0 + fo);
       }
     }
+    if constexpr (ORD) {  // (the fences pin the issue order of the three operand classes)
+      __builtin_amdgcn_sched_barrier(0);
+      load_pw();
+      __builtin_amdgcn_sched_barrier(0);
+      load_xa();
+    }
     __builtin_amdgcn_sched_barrier(0);  // all loads in flight together
+    if constexpr (TRACE && NGT > 0 && FWD) {
+      if (trs) {  // loads issued after the first class: ORD pw + xa, else pw + the factors
+        unsigned long long* t2 = trs + (size_t)(bid * 4 + wave) * 2;
+        constexpr int NLATE = ORD ? RTW * G2 : 2 * NGT;
+        if (wave < 2) trace_stamp_vm<NLATE + 4>(t2, 0);
+        else trace_stamp_vm<NLATE>(t2, 0);
+      }
+    }
     if (TRACE) trace_stamp(trw, 1);
     f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
 #pragma unroll
@@ -1311,6 +1395,73 @@ __global__ __launch_bounds__(256) void mlp_fwdapply_kernel(
     unsigned long long* __restrict__ tr = nullptr) {
   fwdapply_block<NGT, XW, TRACE, TWO, KSX, FWD>(blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr,
                                                 stats, stats_ring, B, stats_on, xg, tr);
+}
+
+// ---------------------------------------------------------------------------
+// Lean entry points of the single-GPU two-launch step (28 K slices, row-major factors): the
+// bodies above (fwdapply_block<.., 0, .., KS3> / head_row<.., RM>) behind kernel arguments of
+// scalars and pointers only -- 16 dwords for the first launch, 7 for the head -- which the file
+// is built to PRELOAD into user SGPRs at wave launch (-amdgpu-kernarg-preload-count=16; by-value
+// structs such as Bufs / MlpXg are never preloaded).  14 dwords fit beside the kernarg segment
+// pointer, so `stats` (read by one wave of one block) comes last and is fetched the usual way.  The workspace regions come from the base
+// pointer through ws_layout, the host launchers' own offsets.
+//   flags = B | stats_on << 9 | stats_ring << 10 (lean_flags)
+// The data-parallel engines, mlp_fwdapply_launch / mlp_head2_launch and the opt-in fused flush
+// keep mlp_fwdapply_kernel / mlp_head_kernel.
+
+template <int NGT, bool TRACE, bool FWD>
+__device__ __forceinline__ void lean_fwdapply_body(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, int* __restrict__ ctr,
+    float* __restrict__ stats, float lr, int flags, unsigned long long* __restrict__ tr,
+    unsigned long long* __restrict__ trs) {
+  const int B = flags & 511, stats_on = (flags >> 9) & 1, stats_ring = flags >> 10;
+  const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
+  fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true>(
+      blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{}, tr,
+      trs);
+}
+
+template <int NGT, bool FWD = true>
+__global__ __launch_bounds__(256) void mlp_lean_fwdapply_kernel(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, float lr, int flags,
+    int* __restrict__ ctr, float* __restrict__ stats) {
+  lean_fwdapply_body<NGT, false, FWD>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags, nullptr,
+                                      nullptr);
+}
+
+template <int NGT>
+__global__ __launch_bounds__(256) void mlp_lean_fwdapply_trace_kernel(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, float lr, int flags,
+    int* __restrict__ ctr, float* __restrict__ stats, unsigned long long* __restrict__ tr,
+    unsigned long long* __restrict__ trs) {
+  lean_fwdapply_body<NGT, true, true>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags, tr, trs);
+}
+
+template <int NGT, bool TRACE>
+__device__ __forceinline__ void lean_head_body(const float* __restrict__ p,
+                                               const int* __restrict__ labels,
+                                               float* __restrict__ ws, int B,
+                                               unsigned long long* __restrict__ tr) {
+  const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
+  head_row<false, TRACE, 0, KS3, true, NGT>(blockIdx.x, threadIdx.x, p, p, 0.f, nullptr, labels, w,
+                                            B, tr, MlpXg{}, nullptr);
+}
+
+template <int NGT>
+__global__ __launch_bounds__(64) void mlp_lean_head_kernel(const float* __restrict__ p,
+                                                           const int* __restrict__ labels,
+                                                           float* __restrict__ ws, int B) {
+  lean_head_body<NGT, false>(p, labels, ws, B, nullptr);
+}
+
+template <int NGT>
+__global__ __launch_bounds__(64) void mlp_lean_head_trace_kernel(
+    const float* __restrict__ p, const int* __restrict__ labels, float* __restrict__ ws, int B,
+    unsigned long long* __restrict__ tr) {
+  lean_head_body<NGT, true>(p, labels, ws, B, tr);
 }
 
 // Terminal step of a launched region with the flush folded in (opt-in,
@@ -1726,18 +1877,7 @@ __global__ __launch_bounds__(256) void mlp_wgrad_factor_kernel(
 // host launchers
 // ---------------------------------------------------------------------------
 static mlp::Bufs make_bufs(float* ws, int B) {
-  using namespace mlp;
-  const int BP = ((B + 15) / 16) * 16;
-  Bufs b;
-  b.slab = ws;
-  b.hbuf = b.slab + (size_t)NSLAB_MAX * BP * HP;
-  b.dz1T = b.hbuf + (size_t)BP * HP;
-  b.dlT = b.dz1T + (size_t)HP * BP;
-  b.rowstat = b.dlT + (size_t)16 * BP;
-  b.sync = reinterpret_cast<int*>(b.rowstat + (size_t)2 * BP);
-  b.dz1R = b.rowstat + (size_t)2 * BP + 4;
-  b.dlR = b.dz1R + (size_t)BP * HP;
-  return b;
+  return mlp::ws_bufs(ws, ((B + 15) / 16) * 16);
 }
 
 // TF checkpoint layout <-> the kernels' flat layout of the MLP parameters / gradients (the
@@ -1797,9 +1937,7 @@ void mlp_tf_layout_launch(const float* src, float* dst, int to_tf, const float* 
 
 long long mlp_workspace_floats(int B) {
   using namespace mlp;
-  const long long BP = ((B + 15) / 16) * 16;
-  return (long long)NSLAB_MAX * BP * HP + BP * HP + HP * BP + 16 * BP + 2 * BP + 4 + BP * HP +
-         16 * BP;
+  return ws_layout(((B + 15) / 16) * 16).total;
 }
 
 // Float offsets of the row-major factor regions in a workspace of batch B: out = {dz1R, dlR,
@@ -2014,6 +2152,72 @@ static int mlp_single_ks() {
   return ks;
 }
 
+// The lean pair (mlp_lean_fwdapply_kernel / mlp_lean_head_kernel): what step_pipelined, the
+// graph capture, mlp_run_pipelined_launch and the flush run at the default K slicing.
+static int lean_flags(int B, int stats_on, const float* stats, int stats_ring) {
+  if (!stats) stats_ring = 1;
+  if (stats_ring < 1 || stats_ring >= (1 << 21))
+    throw std::runtime_error("fused MLP step: stats_ring must be in [1, 2^21)");
+  return B | (stats_on ? 1 << 9 : 0) | stats_ring << 10;
+}
+
+template <bool FWD>
+static void lean_first_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
+                              const float* x, float* ws, int* ctr, float* stats, int stats_ring,
+                              int B, int stats_on, hipStream_t stream) {
+  using namespace mlp;
+  const int flags = lean_flags(B, stats_on, stats, stats_ring);
+  dim3 grid(HT * KS3 + HT), block(256);
+  if ((B + 15) / 16 == 7)
+    hipLaunchKernelGGL((mlp_lean_fwdapply_kernel<7, FWD>), grid, block, 0, stream, p_old, p_new,
+                       x_prev, x, ws, lr, flags, ctr, stats);
+  else
+    hipLaunchKernelGGL((mlp_lean_fwdapply_kernel<0, FWD>), grid, block, 0, stream, p_old, p_new,
+                       x_prev, x, ws, lr, flags, ctr, stats);
+}
+
+static void lean_head_launch(const float* p, const int* labels, float* ws, int B,
+                             hipStream_t stream) {
+  using namespace mlp;
+  if ((B + 15) / 16 == 7)
+    hipLaunchKernelGGL((mlp_lean_head_kernel<7>), dim3(B), dim3(64), 0, stream, p, labels, ws, B);
+  else
+    hipLaunchKernelGGL((mlp_lean_head_kernel<0>), dim3(B), dim3(64), 0, stream, p, labels, ws, B);
+}
+
+void mlp_head2_launch(const float* p, const int* labels, float* ws, int B, hipStream_t stream,
+                      int nslab);
+void mlp_fwdapply_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
+                         const float* x, float* ws, int* ctr, float* stats, int stats_ring, int B,
+                         int stats_on, hipStream_t stream, int ks);
+
+// First launch of the single-GPU two-launch step: the lean kernel, or with DTFX_MLP_KS=14 the
+// 14-slice mlp_fwdapply_kernel.
+void mlp_lean_fwdapply_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
+                              const float* x, float* ws, int* ctr, float* stats, int stats_ring,
+                              int B, int stats_on, hipStream_t stream) {
+  if (mlp_single_ks() != mlp::KS3)
+    return mlp_fwdapply_launch(p_old, p_new, lr, x_prev, x, ws, ctr, stats, stats_ring, B, stats_on,
+                               stream, mlp::KS2);
+  check_b(B);
+  if (!p_old || !p_new || p_old == p_new || !x_prev || !x || !ctr || !ws)
+    throw std::runtime_error(
+        "mlp_lean_fwdapply: needs distinct ping-pong buffers, both batches, ctr");
+  lean_first_launch<true>(p_old, p_new, lr, x_prev, x, ws, ctr, stats, stats_ring, B, stats_on,
+                          stream);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// Its head (row-major factors out); DTFX_MLP_KS=14: mlp_head2_launch.
+void mlp_lean_head_launch(const float* p, const int* labels, float* ws, int B,
+                          hipStream_t stream) {
+  if (mlp_single_ks() != mlp::KS3) return mlp_head2_launch(p, labels, ws, B, stream, mlp::KS2);
+  check_b(B);
+  if (!p || !labels || !ws) throw std::runtime_error("mlp_lean_head: null buffer");
+  lean_head_launch(p, labels, ws, B, stream);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
 // Pipelined single-GPU step (see mlp_fwdapply_kernel): K1' then the head over the K slabs.
 void mlp_fwdapply_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                          const float* x, float* ws, int* ctr, float* stats, int stats_ring, int B,
@@ -2051,9 +2255,9 @@ void mlp_fwdapply_launch(const float* p_old, float* p_new, float lr, const float
 
 // The pending update of the last single-GPU pipelined step (the flush): W1 from step t's
 // factors and its small parameters, p_old -> p_new, with step t's loss / accuracy record and
-// global_step += 1 -- the first launch's apply half alone (mlp_fwdapply_kernel<.., FWD =
-// false>, the single-GPU K slicing), ~half the MFMAs per wave of the 3-launch step's
-// mlp_wgrad_kernel.
+// global_step += 1 -- the first launch's apply half alone (mlp_lean_fwdapply_kernel<.., FWD =
+// false>; DTFX_MLP_KS=14: mlp_fwdapply_kernel<.., KS2, false>), ~half the MFMAs per wave of the
+// 3-launch step's mlp_wgrad_kernel.
 void mlp_apply_launch(const float* p_old, float* p_new, float lr, const float* x_prev, float* ws,
                       int* ctr, float* stats, int stats_ring, int B, hipStream_t stream) {
   using namespace mlp;
@@ -2070,32 +2274,22 @@ void mlp_apply_launch(const float* p_old, float* p_new, float lr, const float* x
     const char* e = std::getenv("DTFX_MLP_FLUSH_FWD");
     return e && std::atoi(e) == 1;
   }();
-  if (ffwd) {
-    if (mlp_single_ks() == KS3) {
-      if (rt7)
-        hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, false, false, KS3>), dim3(HT * KS3 + HT),
-                           dim3(256), 0, stream, p_old, p_new, lr, x_prev, x_prev, w, ctr, stats,
-                           stats_ring, B, 1, MlpXg{}, nullptr);
-      else
-        hipLaunchKernelGGL((mlp_fwdapply_kernel<0, 0, false, false, KS3>), dim3(HT * KS3 + HT),
-                           dim3(256), 0, stream, p_old, p_new, lr, x_prev, x_prev, w, ctr, stats,
-                           stats_ring, B, 1, MlpXg{}, nullptr);
-      DTFX_HIP_CHECK(hipGetLastError());
-      return;
-    }
-  }
-#define DTFX_AP(NGT, KSV)                                                                       \
-  hipLaunchKernelGGL((mlp_fwdapply_kernel<NGT, 0, false, false, KSV, false>), dim3(HT * KSV + HT), \
-                     dim3(256), 0, stream, p_old, p_new, lr, x_prev, x_prev, w, ctr, stats,        \
-                     stats_ring, B, 1, MlpXg{}, nullptr)
-  if (mlp_single_ks() == KS3) {
-    if (rt7) DTFX_AP(7, KS3);
-    else DTFX_AP(0, KS3);
+  if (mlp_single_ks() == KS3) {  // the lean first launch, apply-only (or whole: ffwd)
+    if (ffwd)
+      lean_first_launch<true>(p_old, p_new, lr, x_prev, x_prev, ws, ctr, stats, stats_ring, B, 1,
+                              stream);
+    else
+      lean_first_launch<false>(p_old, p_new, lr, x_prev, x_prev, ws, ctr, stats, stats_ring, B, 1,
+                               stream);
+  } else if (rt7) {
+    hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, false, false, KS2, false>), dim3(HT * KS2 + HT),
+                       dim3(256), 0, stream, p_old, p_new, lr, x_prev, x_prev, w, ctr, stats,
+                       stats_ring, B, 1, MlpXg{}, nullptr);
   } else {
-    if (rt7) DTFX_AP(7, KS2);
-    else DTFX_AP(0, KS2);
+    hipLaunchKernelGGL((mlp_fwdapply_kernel<0, 0, false, false, KS2, false>), dim3(HT * KS2 + HT),
+                       dim3(256), 0, stream, p_old, p_new, lr, x_prev, x_prev, w, ctr, stats,
+                       stats_ring, B, 1, MlpXg{}, nullptr);
   }
-#undef DTFX_AP
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2166,22 +2360,26 @@ void mlp_fwdapply_xg_launch(const float* p_old, float* p_new, float lr, const fl
 }
 
 // Probe: one pipelined step with in-kernel stamps in both launches (trf: (7 * ks + 7) * 4 * 4
-// with ks = mlp_single_ks_query(), trh: B * 4 entries); batch 100 only.
+// with ks = mlp_single_ks_query(), trh: B * 4 entries; trs, optional: the 28-slice first launch's
+// split stamps, (7 * 28 + 7) * 4 * 2); batch 100 only.
 int mlp_single_ks_query() { return mlp_single_ks(); }
 void mlp_pipelined_trace_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                                 const float* x, const int* labels, float* ws, int* ctr,
                                 float* stats, int stats_ring, int B, hipStream_t stream,
-                                unsigned long long* trf, unsigned long long* trh) {
+                                unsigned long long* trf, unsigned long long* trh,
+                                unsigned long long* trs) {
   using namespace mlp;
   check_b(B);
   if ((B + 15) / 16 != 7) throw std::runtime_error("mlp_pipelined_trace: batch 97..112 only");
   const Bufs w = make_bufs(ws, B);
   if (mlp_single_ks() == KS3) {
-    hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, true, false, KS3>), dim3(HT * KS3 + HT), dim3(256),
-                       0, stream, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, 1,
-                       MlpXg{}, trf);
-    hipLaunchKernelGGL((mlp_head_kernel<false, true, 0, KS3, true>), dim3(B), dim3(64), 0, stream,
-                       p_new, p_new, 0.f, nullptr, labels, w, B, trh, MlpXg{}, nullptr);
+    // the lean pair's TRACE instantiations; trs (optional): [(7 * 28 + 7) * 4 waves][2] split
+    // stamps of the first launch (fwdapply_block)
+    hipLaunchKernelGGL((mlp_lean_fwdapply_trace_kernel<7>), dim3(HT * KS3 + HT), dim3(256), 0,
+                       stream, p_old, p_new, x_prev, x, ws, lr,
+                       lean_flags(B, 1, stats, stats_ring), ctr, stats, trf, trs);
+    hipLaunchKernelGGL((mlp_lean_head_trace_kernel<7>), dim3(B), dim3(64), 0, stream,
+                       (const float*)p_new, labels, ws, B, trh);
   } else {
     hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, true>), dim3(HT * KS2 + HT), dim3(256), 0, stream,
                        p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, 1, MlpXg{}, trf);
@@ -2226,8 +2424,8 @@ void mlp_head2_single_launch(const float* p, const int* labels, float* ws, int B
 
 // n pipelined single-GPU steps issued from ONE host call (no Python, no hipGraph): step i
 // trains on batch (pos + i) % nbatches of the device-resident dataset and ping-pongs the
-// parameter buffers exactly like n calls of mlp_fwdapply_launch + mlp_head2_launch.  A graph
-// replay pays ~15 us of submission before its first kernel runs; these launches reach the GPU
+// parameter buffers exactly like n calls of mlp_lean_fwdapply_launch + mlp_lean_head_launch.
+// A graph replay pays ~15 us of submission before its first kernel runs; these launches reach the GPU
 // one by one while the host keeps queueing ahead (host ~2 us per launch < ~4 us of GPU time
 // per launch), so a short run starts at once.  Returns nothing: the caller advances its host
 // mirrors (batch position, parity, pending) by n.
@@ -2307,17 +2505,9 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
       break;
     }
     if (ks3) {
-      if (rt7)
-        hipLaunchKernelGGL((mlp_fwdapply_kernel<7, 0, false, false, KS3>), dim3(HT * KS3 + HT),
-                           dim3(256), 0, stream, po, pn, l, xprev, xcur, w, ctr, stats, stats_ring,
-                           B, pending, MlpXg{}, nullptr);
-      else
-        hipLaunchKernelGGL((mlp_fwdapply_kernel<0, 0, false, false, KS3>), dim3(HT * KS3 + HT),
-                           dim3(256), 0, stream, po, pn, l, xprev, xcur, w, ctr, stats, stats_ring,
-                           B, pending, MlpXg{}, nullptr);
-      hipLaunchKernelGGL((mlp_head_kernel<false, false, 0, KS3, true>), dim3(B), dim3(64), 0,
-                         stream, pn, pn, 0.f, nullptr, labels + (size_t)pos * B, w, B, nullptr,
-                         MlpXg{}, nullptr);
+      lean_first_launch<true>(po, pn, l, xprev, xcur, ws, ctr, stats, stats_ring, B, pending,
+                              stream);
+      lean_head_launch(pn, labels + (size_t)pos * B, ws, B, stream);
     } else {
       if (rt7)
         hipLaunchKernelGGL((mlp_fwdapply_kernel<7>), dim3(HT * KS2 + HT), dim3(256), 0, stream, po,

@@ -35,6 +35,10 @@ CSRC = os.path.join(ROOT, "csrc")
 BUILD = os.path.join(ROOT, "build", "native")
 ARCH = os.environ.get("DTFX_OFFLOAD_ARCH", "gfx950")
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
+# Per-file hipcc flags.  mlp_step.hip: up to 16 kernel-argument dwords are preloaded into user
+# SGPRs at wave launch (scalar and pointer arguments only; the lean step's kernels take nothing
+# else).  The compiler also emits the prologue for firmware that does not preload.
+HIP_FILE_FLAGS = {"mlp_step.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
 
 
 def _pybind_includes():
@@ -104,8 +108,9 @@ def build_hip(verbose=False, force=False):
         obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or not _newer(obj, [src] + headers):
-            jobs.append(([hipcc, "-c", "-x", "hip", src, "-o", obj] + common, obj))
-    inc = sum([["-I", d] for d in _pybind_includes()], [])
+            extra = HIP_FILE_FLAGS.get(os.path.basename(src), [])
+            jobs.append(([hipcc, "-c", "-x", "hip", src, "-o", obj] + common + extra, obj))
+    inc =sum([["-I", d] for d in _pybind_includes()], [])
     for cpp in sorted(glob.glob(os.path.join(src_dir, "*.cpp"))):  # host-side C++ (bindings, RCCL)
         obj = os.path.join(obj_dir, os.path.basename(cpp) + ".o")
         objs.append(obj)

@@ -139,12 +139,14 @@ def step_direct(p, x, labels, ws: StepWorkspace, lr, stats=True):
 
 
 def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, stats=True):
-    """Two-launch single-GPU step: ``mlp_fwdapply`` applies the PREVIOUS step's SGD update
+    """Two-launch single-GPU step: ``mlp_lean_fwdapply`` applies the PREVIOUS step's SGD update
     (from the factors dz1/h/dlogits the last head left in ``ws`` and the previous batch
     ``x_prev``; W1 never materialises a gradient) reading ``p_old`` and writing ``p_new``,
-    and runs this step's forward on the updated W1; ``mlp_head2`` (28 partial z1 slabs:
-    the single-GPU K slicing, ``hip().mlp_single_ks()``; ``single=1``: it leaves dz1 / dlogits
-    row-major, as the next ``mlp_fwdapply`` / ``mlp_apply`` reads them) finishes the step.
+    and runs this step's forward on the updated W1; ``mlp_lean_head`` (28 partial z1 slabs:
+    the single-GPU K slicing, ``hip().mlp_single_ks()``; it leaves dz1 / dlogits row-major,
+    as the next ``mlp_lean_fwdapply`` / ``mlp_apply`` reads them) finishes the step.  The lean
+    pair is the same arithmetic as ``mlp_fwdapply(ks=28)`` + ``mlp_head2(single=1)`` behind
+    packed, preloaded kernel arguments, with phase A's operands requested first.
     ``apply=False`` (nothing pending): a plain copy + forward.  The
     last step's update stays pending until ``flush_pipelined``."""
     _check(x, labels, ws.B)
@@ -153,10 +155,10 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     if p_old.data_ptr() == p_new.data_ptr():
         raise ValueError("the pipelined step needs distinct ping-pong buffers")
     h, s = hip(), stream_handle()
-    h.mlp_fwdapply(ptr(p_old), ptr(p_new), float(lr) if apply else 0.0,
-                   ptr(x_prev if apply else x), ptr(x), ptr(ws.buf), ptr(ws.ctr),
-                   ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, 1 if apply else 0, s)
-    h.mlp_head2(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s, 0, 1)  # (row-major factors)
+    h.mlp_lean_fwdapply(ptr(p_old), ptr(p_new), float(lr) if apply else 0.0,
+                        ptr(x_prev if apply else x), ptr(x), ptr(ws.buf), ptr(ws.ctr),
+                        ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, 1 if apply else 0, s)
+    h.mlp_lean_head(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s)  # (row-major factors)
 
 
 def flush_pipelined(p_old, p_new, x_prev, ws: StepWorkspace, lr, stats=True):

@@ -3,11 +3,13 @@ s_memrealtime stamps (100 MHz; every stamp waits for the wave's outstanding memo
 marks "everything issued before has landed").
 
 Steps 100 and 101 of a 200-step hipGraph chain run the traced kernels (same code, stamps
-added): mlp_fwdapply_kernel<7, 0, true, .., KS> (7 x KS W1-tile blocks x 4 waves: 0 entry,
+added): mlp_lean_fwdapply_trace_kernel<7> (7 x 28 W1-tile blocks x 4 waves: 0 entry,
 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab stored; 7 small-parameter
-blocks: 0, 3; KS = 28, or 14 with DTFX_MLP_KS=14) and mlp_head_kernel<.., KS> (100 one-wave
-blocks: 0 entry, 1 operands landed, 2 compute
-done, 3 stores landed).  Prints per-phase medians / maxima and the kernel-to-kernel gaps
+blocks: 0, 3; with DTFX_MLP_KS=14 mlp_fwdapply_kernel<7, 0, true>, 14 slices) and
+mlp_lean_head_trace_kernel<7> / mlp_head_kernel<.., 14> (100 one-wave blocks: 0 entry, 1 operands
+landed, 2 compute done, 3 stores landed).  The 28-slice first launch also leaves a split stamp
+per wave: its first-issued operand class (the factors dz1R + x_prev) has landed, with the W1
+values and this step's x rows, issued after them, still in flight.  Prints per-phase medians / maxima and the kernel-to-kernel gaps
 (the dependent-launch boundaries a single-launch design would have to beat).
 
     python tools/probes/mlp_pipelined_trace.py > profiles/r3/mlp_trace/pipelined_trace.json
@@ -48,6 +50,7 @@ def main():
     ws = mlp_step.StepWorkspace(B, dev)
     trf = [torch.zeros((NB_W1 + NB_SMALL) * 4 * 4, dtype=torch.int64, device=dev) for _ in range(2)]
     trh = [torch.zeros(B * 4, dtype=torch.int64, device=dev) for _ in range(2)]
+    trs = [torch.zeros((NB_W1 + NB_SMALL) * 4 * 2, dtype=torch.int64, device=dev) for _ in range(2)]
     lr = 1e-4
 
     def step(i, cur, traced):
@@ -55,13 +58,13 @@ def main():
         xp = x[((i - 1) % nb) * B:((i - 1) % nb + 1) * B]
         s = stream_handle()
         if traced is None:
-            h.mlp_fwdapply(ptr(p[cur]), ptr(p[cur ^ 1]), lr, ptr(xp), ptr(xb), ptr(ws.buf),
-                           ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, B, 1, s)
-            h.mlp_head2(ptr(p[cur ^ 1]), ptr(yb), ptr(ws.buf), B, s, 0, 1)
+            h.mlp_lean_fwdapply(ptr(p[cur]), ptr(p[cur ^ 1]), lr, ptr(xp), ptr(xb), ptr(ws.buf),
+                                ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, B, 1, s)
+            h.mlp_lean_head(ptr(p[cur ^ 1]), ptr(yb), ptr(ws.buf), B, s)
         else:
             h.mlp_pipelined_trace(ptr(p[cur]), ptr(p[cur ^ 1]), lr, ptr(xp), ptr(xb), ptr(yb),
                                   ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, B, s,
-                                  ptr(trf[traced]), ptr(trh[traced]))
+                                  ptr(trf[traced]), ptr(trh[traced]), ptr(trs[traced]))
 
     for i in range(20):
         step(i, i & 1, None)
@@ -74,7 +77,7 @@ def main():
             step(i, i & 1, 0 if i == 100 else 1 if i == 101 else None)
     reps = []
     for _ in range(5):
-        for t in trf + trh:
+        for t in trf + trh + trs:
             t.zero_()
         g.replay()
         torch.cuda.synchronize()
@@ -86,6 +89,14 @@ def main():
                                                 (1, 2, "mfma+apply+barrier"),
                                                 (2, 3, "phaseB_fwd+slab_store"),
                                                 (0, 3, "wave_total")])
+        sp = trs[0].view(-1, 2).cpu()[:NB_W1 * 4, 0]
+        if bool((sp > 0).all()):  # (28 slices: the split stamps)
+            d0 = (sp - w1[0][:, 0]).double() / 100.0
+            d1 = (w1[0][:, 1] - sp).double() / 100.0
+            f_ph["entry->factors+x_prev_landed"] = [round(float(d0.median()), 3),
+                                                    round(float(d0.max()), 3)]
+            f_ph["factors+x_prev_landed->all_landed"] = [round(float(d1.median()), 3),
+                                                         round(float(d1.max()), 3)]
         s_ph, _, _, s_end = phases(sm[0], [(0, 3, "small_block_total")])
         h_ph, h0, h0max, h_end = phases(hd[0], [(0, 1, "entry->operands_landed"),
                                                 (1, 2, "compute"), (2, 3, "stores_landed"),
