@@ -312,6 +312,19 @@ __device__ __forceinline__ void head_allgather(const MlpXg& xg, unsigned ep, int
 // RM: the factors are stored row-major (dz1R / dlR) for mlp_fwdapply_kernel<.., 0, .., KS3>
 // and NOT to dz1T / dlT.
 // NGT > 0: the batch is padded to NGT * 16 rows at compile time.
+// Load placement (ISA read and A/B measured: profiles/head_label_load/README.md).  Everything
+// behind the scheduling fence is ONE unmasked instruction stream up to the hbuf store: a lane's
+// two units are summed as a pair (one v_pk_add_f32 per slab plane, started from 0, planes in
+// order) and masked by select, where two exec-masked blocks used to run one 28-add chain each.
+// With no branch behind the fence the compiler issues the label's load -- a plain scalar load,
+// the address is wave-uniform -- at the head of the kernel, ahead of the operand loads; it used
+// to sink it behind the first unit's chain and wait for it in the tail.  The label is NOT read
+// with a per-lane vector load (row offset laundered through a VGPR): that form puts a cold
+// 64-lane load at the head of the in-order vmcnt queue and was measured slower than the late
+// scalar load.  Loads from a `const __restrict__` kernel argument are constant memory to the
+// compiler and carry no ordering against the fence, so the b1 / W2 / b2 loads go through a
+// laundered global pointer: ordinary loads, which stay in front of it.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false, int NGT = 0>
 __device__ __forceinline__ void head_row(
     const int row, const int lane, const float* __restrict__ p_old,
@@ -323,6 +336,8 @@ __device__ __forceinline__ void head_row(
   if (TRACE) trace_stamp(tr, row * 4 + 0);
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
   const int y = labels[row];
+  float invB = 1.f / (float)B;  // (an IEEE division sequence: pinned here, under the memory wait)
+  asm volatile("" : "+v"(invB));
   const unsigned ep = XW > 0 ? xg.epochs[MLP_XG_HEAD_EPOCH + row] + 1 : 0u;
   const bool publish = APPLY && row == 0;
 
@@ -331,30 +346,33 @@ __device__ __forceinline__ void head_row(
   // z1 slabs, b1, the 10 W2 columns -- arrives as one 8-B load per pair: 49 load
   // instructions per lane instead of 88 (more than the 63 a wave can keep in flight:
   // the 28-slab step waited out a second round trip here).
-  float hv[2], w2[2][C], zs[2], b1v[2];
+  float hv[2], w2[2][C], b1v[2];
   int jj[2];
   bool jv[2];
   const int j0 = min(2 * lane, H - 2);  // (H even: j0, j0 + 1 always a valid, aligned pair)
+  const bool pv = lane < H / 2;         // (so both units of a lane are live or neither is)
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     jv[u] = 2 * lane + u < H;
     jj[u] = j0 + u;
-    zs[u] = 0.f;
   }
+  f32x2 sv[NSLAB];
 #pragma unroll
-  for (int s = 0; s < NSLAB; ++s) {
-    const float2 v = *reinterpret_cast<const float2*>(&w.slab[((size_t)s * BP + row) * HP + j0]);
-    zs[0] += v.x;
-    zs[1] += v.y;
-  }
+  for (int s = 0; s < NSLAB; ++s)
+    sv[s] = *reinterpret_cast<const f32x2*>(&w.slab[((size_t)s * BP + row) * HP + j0]);
+  typedef const __attribute__((address_space(1))) float* gcf;
+  typedef const __attribute__((address_space(1))) f32x2* gcf2;
+  unsigned long long pa = (unsigned long long)p_old;
+  asm("" : "+s"(pa));
+  const gcf pq = (gcf)pa;
   {
-    const float2 v = *reinterpret_cast<const float2*>(&p_old[OFF_B1 + j0]);
+    const f32x2 v = *(gcf2)(pq + OFF_B1 + j0);
     b1v[0] = v.x;
     b1v[1] = v.y;
   }
 #pragma unroll
   for (int c = 0; c < C; ++c) {
-    const float2 v = *reinterpret_cast<const float2*>(&p_old[OFF_W2 + c * H + j0]);
+    const f32x2 v = *(gcf2)(pq + OFF_W2 + c * H + j0);
     w2[0][c] = v.x;
     w2[1][c] = v.y;
   }
@@ -362,7 +380,7 @@ __device__ __forceinline__ void head_row(
   // 16-lane rows carry the same values)
   const int cl = lane & 15, cc = min(cl, C - 1);
   const bool clive = cl < C;
-  float b2l = p_old[OFF_B2 + cc];
+  float b2l = pq[OFF_B2 + cc];
   float gb1[2], gw2[2][C], gb2l = 0.f;
   if (APPLY) {
 #pragma unroll
@@ -394,13 +412,19 @@ __device__ __forceinline__ void head_row(
     }
   }
   if (TRACE) trace_stamp(tr, row * 4 + 1);
+  f32x2 zp = {0.f, 0.f};  // (from 0, planes in order: 0 + (-0) is +0, a sum begun at plane 0 not)
+#pragma unroll
+  for (int s = 0; s < NSLAB; ++s) zp += sv[s];
+  const float zs[2] = {zp.x, zp.y};
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    hv[u] = jv[u] ? sigmoidf_(zs[u] + b1v[u]) : 0.f;
+    const float sg = sigmoidf_(zs[u] + b1v[u]);
+    hv[u] = pv ? sg : 0.f;
 #pragma unroll
-    for (int c = 0; c < C; ++c) w2[u][c] = jv[u] ? w2[u][c] : 0.f;
-    if (jv[u]) w.hbuf[(size_t)row * HP + jj[u]] = hv[u];
+    for (int c = 0; c < C; ++c) w2[u][c] = pv ? w2[u][c] : 0.f;
   }
+  if (pv)
+    *reinterpret_cast<float2*>(&w.hbuf[(size_t)row * HP + 2 * lane]) = make_float2(hv[0], hv[1]);
   // logits = h . W2 + b2: a reduce-scatter leaves class cl's logit on lane l, and the softmax
   // runs ONE class per lane -- one v_exp_f32 per lane, 16-lane row reductions for the max and
   // the denominator -- where all 64 lanes used to repeat the 10-class chains on the same ten
@@ -415,7 +439,7 @@ __device__ __forceinline__ void head_row(
   const int am = atmax ? __builtin_ctzll(atmax) : 0;
   const float ec = clive ? __expf(lgc - m) : 0.f;
   const float se = row_sum16(ec);
-  const float inv = fast_rcp(se), invB = 1.f / (float)B;
+  const float inv = fast_rcp(se);
   const int yu = __builtin_amdgcn_readfirstlane(y);  // (wave-uniform: the row's label)
   const float mydl = (ec * inv - (cl == yu ? 1.f : 0.f)) * invB;  // dlogits of class cl
   const float ly = (unsigned)yu < (unsigned)C  // the label's logit (0 for a label out of range)
