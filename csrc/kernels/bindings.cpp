@@ -72,6 +72,10 @@ void act_bwd_launch(long long, int, const float*, const float*, float*, hipStrea
 void act_fwd_launch(long long, int, const float*, float*, hipStream_t);
 void shuffle_rows_launch(float*, const float*, int*, const int*, long long, int, long long,
                          long long, unsigned, unsigned, hipStream_t);
+void mlp_eval_launch(const float*, const float*, const int*, int, void*, int*, float*, hipStream_t);
+int mlp_eval_acc_bytes();
+int mlp_eval_row_tile();
+int mlp_eval_max_rows();
 }  // namespace dtfx
 
 void register_rccl(py::module_& m);
@@ -321,6 +325,21 @@ PYBIND11_MODULE(_hip, m) {
      py::arg("epoch"), py::arg("stream"),
      "per-epoch reshuffle gather: dst[w][j] = src[w][perm(seed, epoch, n)[j]] over `planes` "
      "planes of [n, 784] f32 (strides in floats) and the int32 labels (csrc/kernels/shuffle.hip)");
+  m.def("mlp_eval", [](uintptr_t p, uintptr_t x, uintptr_t lab, int n, uintptr_t acc,
+                        uintptr_t pred, uintptr_t probs, uintptr_t s) {
+    dtfx::mlp_eval_launch(P<const float>(p), P<const float>(x), P<const int>(lab), n, P<void>(acc),
+                          P<int>(pred), P<float>(probs), S(s));
+  }, py::arg("p"), py::arg("x"), py::arg("labels"), py::arg("n"), py::arg("acc"), py::arg("pred"),
+     py::arg("probs"), py::arg("stream"),
+     "fused evaluation of the 784-100-10 MLP on n rows (csrc/kernels/mlp_eval.hip): pred int32 "
+     "[n] / probs f32 [n, 10] optional (0); labels 0: predict only, acc untouched; otherwise acc "
+     "(mlp_eval_acc_bytes bytes) is zeroed on the stream and then accumulated");
+  m.def("mlp_eval_acc_bytes", &dtfx::mlp_eval_acc_bytes,
+        "bytes of the accumulator block: int64 loss sum (2^-32 units), int32 correct, int32 "
+        "count, int32 confusion [10][10] indexed [label][predicted]");
+  m.def("mlp_eval_row_tile", &dtfx::mlp_eval_row_tile, "rows per workgroup of mlp_eval");
+  m.def("mlp_eval_max_rows", &dtfx::mlp_eval_max_rows,
+        "largest n of mlp_eval (the fixed-point loss sum cannot overflow up to it)");
   m.def("calib", [](int mode, int grid, int block, uintptr_t ctr, uintptr_t data, uintptr_t out,
                     uintptr_t s) {
     dtfx::calib_launch(mode, grid, block, P<const int>(ctr), P<const float>(data), P<float>(out),

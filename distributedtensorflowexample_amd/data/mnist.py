@@ -132,6 +132,13 @@ def synthesize_images(labels, test_images, test_labels, seed=0, noise=0.25, max_
     return out
 
 
+def read_test_set(train_dir=None, one_hot=False):
+    """The 10,000-image test set alone (no training images are read or synthesized)."""
+    d = train_dir or DEFAULT_DIR
+    return DataSet(read_idx(os.path.join(d, TEST_IMAGES)), read_idx(os.path.join(d, TEST_LABELS)),
+                   one_hot)
+
+
 def read_data_sets(train_dir=None, one_hot=True, validation_size=5000, seed=None,
                    synthetic_seed=0):
     d = train_dir or DEFAULT_DIR

@@ -181,6 +181,11 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_string("device", "auto", "auto | cuda | cpu (worker compute device)", fv)
     DEFINE_integer("log_every", 100, "Print step/cost/speed every N global steps", fv)
     DEFINE_integer("eval_every", 10000, "Test accuracy every N global steps", fv)
+    DEFINE_boolean("eval_summaries", False,
+                   "At each --eval_every evaluation the chief also writes the scalars test_loss "
+                   "and test_accuracy at that global step to its event file", fv)
+    DEFINE_string("eval_output", "", "--job_name eval: save the int32 test-set predictions to "
+                  "this .npy file", fv)
     DEFINE_float("save_model_secs", 30.0, "Chief checkpoint interval (Supervisor)", fv)
     DEFINE_float("save_summaries_secs", 30.0, "Chief step-rate summary interval", fv)
     DEFINE_boolean("use_locking", False, "Serialize PS updates per variable", fv)

@@ -1,0 +1,69 @@
+"""``--job_name eval``: evaluate the latest checkpoint of a log directory on the test set.
+
+    python main.py --job_name eval --logdir DIR [--data_dir ...] [--device auto|cuda|cpu]
+                   [--eval_output FILE.npy]
+
+No server and no process group is started.  The checkpoint (TF V2 bundle with the
+reference's variable names, train/saver.py) is restored into the flat parameter buffer and
+run through ``ops.mlp_eval.evaluate``: the fused one-launch kernel on a GPU, the CPU path of
+the same op with ``--device cpu`` (or on a machine without a GPU).  Prints the checkpoint's
+global step, the test accuracy, the test loss and the 10 x 10 confusion matrix
+([label][predicted]); ``--eval_output`` saves the int32 predictions.
+"""
+from __future__ import annotations
+
+import sys
+
+import numpy as np
+import torch
+
+from ..data.mnist import read_test_set
+from ..ops import mlp_eval, mlp_step
+from .saver import latest_checkpoint, load_checkpoint
+from .worker import FUSED_TF_SHAPES, REFERENCE_MLP_NAMES, tf_vars_to_flat
+
+STEP_NAME = "global/global_step"
+
+
+def restore_flat(logdir):
+    """(flat parameters on the CPU, global step, checkpoint prefix) of ``logdir``'s latest
+    checkpoint; ``SystemExit`` with a message when there is none or it is not the reference
+    784-100-10 model."""
+    prefix = latest_checkpoint(logdir)
+    if prefix is None:
+        raise SystemExit("eval: no checkpoint in %r" % logdir)
+    values = load_checkpoint(prefix)
+    for name, shape in zip(REFERENCE_MLP_NAMES, FUSED_TF_SHAPES):
+        if name not in values:
+            raise SystemExit("eval: checkpoint %s lacks variable %r" % (prefix, name))
+        if tuple(values[name].shape) != tuple(shape):
+            raise SystemExit("eval: checkpoint %s holds %s shaped %s, the reference 784-100-10 "
+                             "model needs %s" % (prefix, name, tuple(values[name].shape),
+                                                 tuple(shape)))
+    flat = tf_vars_to_flat({k: values[k].float() for k in REFERENCE_MLP_NAMES},
+                           torch.zeros(mlp_step.NPARAM))
+    step = int(values[STEP_NAME]) if STEP_NAME in values else 0
+    return flat, step, prefix
+
+
+def eval_job(flags, log=print):
+    flat, step, _ = restore_flat(flags.logdir)
+    want = str(getattr(flags, "device", "auto") or "auto")
+    if want == "auto":
+        want = "cuda" if torch.cuda.is_available() else "cpu"
+    dev = torch.device(want)
+    test = read_test_set(flags.data_dir or None)
+    x = torch.from_numpy(np.ascontiguousarray(test.images, np.float32)).to(dev)
+    y = torch.from_numpy(np.asarray(test.labels).astype(np.int32)).to(dev)
+    out = str(getattr(flags, "eval_output", "") or "")
+    res = mlp_eval.evaluate(flat.to(dev), x, y, predictions=bool(out))
+    log("global_step: {}".format(step))
+    log("test accuracy: {}".format(res.accuracy))
+    log("test loss: {}".format(res.loss))
+    log("confusion matrix (rows: label, columns: predicted):")
+    for row in res.confusion.tolist():
+        log(" ".join("%5d" % v for v in row))
+    if out:
+        np.save(out, res.pred.cpu().numpy().astype(np.int32))
+    sys.stdout.flush()
+    return 0

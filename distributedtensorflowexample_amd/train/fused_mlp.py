@@ -205,6 +205,17 @@ class FusedMLPTrainer:
         raise RuntimeError("snapshot(): the pending update is a peer exchange; flush() on "
                            "every rank first")
 
+    def evaluate(self, x, labels=None, **kw):
+        """``ops.mlp_eval.evaluate`` of the parameters after every step run so far on ``x``
+        [n, 784] / ``labels`` (int32 [n]): one fused launch, no host synchronisation; the
+        keyword arguments (``predictions``, ``probs``, ``acc``) are the op's.  The parameters
+        are ``snapshot()``'s, by its rules: a pending pipelined update on one GPU is flushed,
+        the all-reduce engine's pending gradient is applied to a copy, a pending peer exchange
+        raises.  ``global_step()`` is unchanged."""
+        from ..ops import mlp_eval
+
+        return mlp_eval.evaluate(self.snapshot(), x, labels, **kw)
+
     def load_params(self, p):
         self.bufs[self.cur].copy_(p)
         self.pending = False

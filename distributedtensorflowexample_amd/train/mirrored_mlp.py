@@ -217,12 +217,26 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     test_x = torch.from_numpy(dataset.test.images).float().to(dev)
     test_y = dataset.test.labels.argmax(1) if dataset.test.labels.ndim == 2 else dataset.test.labels
 
-    def test_accuracy():
+    test_y_dev = torch.from_numpy(test_y.astype("int32")).to(dev) if use_gpu else None
+    eval_summaries = bool(getattr(flags, "eval_summaries", False))
+
+    def test_eval():
+        """(test accuracy, test loss or None): on the GPU the one-launch evaluation kernel
+        (ops/mlp_eval.py) through the trainer; the CPU autograd path keeps the generic
+        forward (and computes the loss only where --eval_summaries asks for it)."""
+        if use_gpu:
+            res = tr.evaluate(test_x, test_y_dev)
+            return float(res.accuracy), float(res.loss)
         p = get_params()
         W1t, b1, W2t, b2 = mlp_step.unflatten(p)
         h = nn.gemm(test_x, W1t, trans_b=True, bias=b1, act="sigmoid")
         logits = nn.gemm(h, W2t, trans_b=True, bias=b2)
-        return float((logits.argmax(1).cpu().numpy() == test_y).mean())
+        acc = float((logits.argmax(1).cpu().numpy() == test_y).mean())
+        if not eval_summaries:
+            return acc, None
+        lab = torch.from_numpy(test_y.astype("int64"))
+        loss = (torch.logsumexp(logits, 1) - logits.gather(1, lab[:, None])[:, 0]).mean()
+        return acc, float(loss)
 
     history = []
     # fail-fast: a rank whose peer died aborts its communicator and exits (non-zero)
@@ -273,7 +287,10 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                     step, cost, float((step - start_step) / max(elapsed, 1e-9))))
                 start_time, start_step = time.time(), step
             if is_chief and step % int(flags.eval_every) == 0:
-                log("test accuracy: {}".format(test_accuracy()))
+                t_acc, t_loss = test_eval()
+                log("test accuracy: {}".format(t_acc))
+                if eval_summaries and writer is not None:
+                    writer.add_scalars({"test_loss": t_loss, "test_accuracy": t_acc}, step)
             k = int(getattr(flags, "check_replicas_every", 0) or 0)
             if k > 0 and world > 1 and step % k == 0:
                 from ..parallel.mirrored import assert_replicas_identical

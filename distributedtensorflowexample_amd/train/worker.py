@@ -29,7 +29,7 @@ import torch
 
 from .. import variables as vs
 from ..models.dense import make_ps_model
-from ..ops import mlp_step, nn
+from ..ops import mlp_step
 from ..parallel.ps import PSVariableStore, replica_device_setter
 from ..utils.summary import FileWriter
 from .saver import FastSaver
@@ -304,25 +304,44 @@ class Worker:
         loss, acc = self.ws.stats[self._rec_slot].tolist()
         return float(loss), float(acc)
 
-    def accuracy(self, images, labels):
-        """worker.py:87-90,150-154 on the local replica: the 10k-image test accuracy.  The
-        test set is uploaded once and stays resident; on the GPU the forward is the
-        hand-written GEMM with the bias + sigmoid epilogue fused (nn.gemm / nn.dense)."""
+    def evaluate(self, images, labels):
+        """worker.py:87-90,150-154 on the local replica: (test accuracy, test loss or None)
+        over the 10k test images.  The test set is uploaded once and stays resident; the
+        fused GPU worker (the reference 784-100-10 model) runs the one-launch evaluation
+        kernel (ops/mlp_eval.py), which also gives the loss; other models keep the generic
+        forward and report the accuracy alone."""
         if self._test is None or self._test[0] is not images:
             x = torch.from_numpy(np.ascontiguousarray(images, np.float32)).to(self.device)
             y = np.asarray(labels)
             y = torch.from_numpy(y.argmax(1) if y.ndim == 2 else y).to(self.device)
+            if self.use_fused:
+                y = y.to(torch.int32)
             self._test = (images, x, y)
         _, x, y = self._test
         self._land_pull()
         with torch.no_grad():
             if self.use_fused:
-                W1t, b1, W2t, b2 = mlp_step.unflatten(self.params)
-                h = nn.gemm(x, W1t, trans_b=True, bias=b1, act="sigmoid")
-                logits = nn.gemm(h, W2t, trans_b=True, bias=b2)
-            else:
-                logits = self.model.logits(self.local, x)
-            return float((logits.argmax(1) == y).float().mean())
+                from ..ops import mlp_eval
+
+                res = mlp_eval.evaluate(self.params, x, y)
+                return float(res.accuracy), float(res.loss)
+            logits = self.model.logits(self.local, x)
+            return float((logits.argmax(1) == y).float().mean()), None
+
+    def accuracy(self, images, labels):
+        """The test accuracy of :meth:`evaluate`."""
+        return self.evaluate(images, labels)[0]
+
+    def _log_eval(self, dataset, step):
+        """The reference's ``test accuracy`` line (worker.py:150-154); with --eval_summaries
+        the chief also writes the scalars test_accuracy / test_loss at ``step``."""
+        acc, loss = self.evaluate(dataset.test.images, dataset.test.labels)
+        self.log("test accuracy: {}".format(acc))
+        if self.is_chief and bool(getattr(self.flags, "eval_summaries", False)):
+            vals = {"test_accuracy": acc}
+            if loss is not None:
+                vals["test_loss"] = loss
+            self.summary_writer.add_scalars(vals, step)
 
     def graph_def(self):
         """The reference graph over this worker's registry variables (utils/graph.py), or None
@@ -405,8 +424,7 @@ class Worker:
                         start_time = time.time()
                         start_step = step
                     if step % eval_every == 0:
-                        self.log("test accuracy: {}".format(
-                            self.accuracy(dataset.test.images, dataset.test.labels)))
+                        self._log_eval(dataset, step)
                     if step >= fl.training_steps:
                         break
                     if max_steps is not None and local_steps >= max_steps:
@@ -458,8 +476,7 @@ class Worker:
                     start_time = time.time()
                     start_step = step
                 if step % eval_every == 0:
-                    self.log("test accuracy: {}".format(
-                        self.accuracy(dataset.test.images, dataset.test.labels)))
+                    self._log_eval(dataset, step)
                 if step >= fl.training_steps:
                     break
                 if max_steps is not None and local_steps >= max_steps:

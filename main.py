@@ -4,6 +4,7 @@ Same flags and defaults as the reference (main.py:28-37), same role dispatch:
 
     python main.py --job_name ps --task_index 0 --num_workers 2 --num_gpus 1
     python main.py --job_name worker --task_index 0 --num_workers 2 --num_gpus 1
+    python main.py --job_name eval --logdir DIR [--device cpu] [--eval_output FILE.npy]
 
 ``--strategy ps_async`` (default) reproduces the reference's asynchronous
 parameter-server SGD (native C++ PS over TCP, fused HIP kernels on the
@@ -46,6 +47,11 @@ def main(argv=None):
 
     _install_signal_handlers()
 
+    if FLAGS.job_name == "eval":
+        # the latest checkpoint of --logdir on the test set: no server, no process group
+        from distributedtensorflowexample_amd.train.eval_job import eval_job
+
+        return eval_job(FLAGS)
     if FLAGS.strategy == "mirrored" and FLAGS.model != "mlp":
         from distributedtensorflowexample_amd.train.mirrored_mlp import shutdown_mirrored
         from distributedtensorflowexample_amd.train.mirrored_models import train_model_mirrored
@@ -111,7 +117,7 @@ def main(argv=None):
         worker = Worker(FLAGS.job_name, FLAGS.task_index, server, FLAGS, device=FLAGS.device)
         worker.learn(mnist)
     else:
-        raise SystemExit("--job_name must be 'ps' or 'worker'")
+        raise SystemExit("--job_name must be 'ps', 'worker' or 'eval'")
     return 0
 
 
