@@ -14,6 +14,8 @@
 //                     use_locking=False -> plain read-modify-write, lock-free / Hogwild like
 //                     TF's default; use_locking=True -> one f32 atomic add per element)
 //   gps_fetch_add     store.global_step += delta, old value returned (worker.py:32,141)
+//   gps_sync_join / gps_sync_push   --sync_replicas: ticket of the open round, gradient into the
+//                     ticket's slot; the R-th arrival of a chunk applies the mean (below)
 #include "common.h"
 
 #include <stdexcept>
@@ -64,7 +66,174 @@ __global__ void gps_fetch_add_kernel(unsigned long long* ctr, long long delta,
     reinterpret_cast<float*>(out + 1)[threadIdx.x] = extra[threadIdx.x];
 }
 
+// ---------------------------------------------------------------------------------------------
+// Synchronous replicas (tf.train.SyncReplicasOptimizer on the store): a push is the two launches
+// below, back to back on the worker's stream.  No kernel waits on another process: both run to
+// completion, and the wait for the round to close is a host poll of the round word
+// (parallel/gpu_ps_sync.py).  Sums are slab sums in ticket order (no float atomics), so a round
+// is bitwise reproducible for a given arrival order.
+//
+// Sync control region (after the control block; layout in gpu_ps.cpp):
+//   u64 round word  (round << 32) | tickets_taken      u32 chunks_done      u32 R
+//   u32 arrivals[ceil(n / 1024)]
+// followed by R gradient slots of n f32 each.
+
+enum : unsigned { GPS_JOINED = 0, GPS_STALE = 1, GPS_AHEAD = 2, GPS_LATE = 3, GPS_CONTENDED = 4 };
+constexpr int kJoinRetries = 1 << 16;
+
+// One thread.  dec[0] = status, dec[1] = ticket, dec[2] = round seen, dec[3] = tickets seen;
+// dec[4 ..] = `nextra` f32 words copied from `extra` (the step's loss / accuracy record), so
+// one read-back serves both.  The loop retries only when another worker's CAS won the word in
+// between (at most R - 1 times per round in a correct run); the bound ends it regardless.
+__global__ void gps_sync_join_kernel(unsigned long long* round_word, unsigned local_step,
+                                     unsigned R, unsigned* dec, const float* extra, int nextra) {
+  if (threadIdx.x == 0) {
+    unsigned long long w =
+        __hip_atomic_load(round_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    unsigned status = GPS_CONTENDED;
+    for (int it = 0; it < kJoinRetries; ++it) {
+      const unsigned round = (unsigned)(w >> 32), taken = (unsigned)w;
+      if (local_step < round) {
+        status = GPS_STALE;
+        break;
+      }
+      if (local_step > round) {
+        status = GPS_AHEAD;
+        break;
+      }
+      if (taken >= R) {
+        status = GPS_LATE;
+        break;
+      }
+      // on failure `w` is reloaded with the word's current value
+      if (__hip_atomic_compare_exchange_strong(round_word, &w, w + 1, __ATOMIC_RELAXED,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) {
+        status = GPS_JOINED;
+        break;
+      }
+    }
+    dec[0] = status;
+    dec[1] = (unsigned)w;  // JOINED: the ticket (the count before this worker's increment)
+    dec[2] = (unsigned)(w >> 32);
+    dec[3] = (unsigned)w;
+  }
+  if ((int)threadIdx.x < nextra) reinterpret_cast<float*>(dec + 4)[threadIdx.x] = extra[threadIdx.x];
+}
+
+// Why a worker of round r+1 never meets state of round r.  It can only JOIN after the round
+// word reads r+1, and that word is published last, by the one block that completed the last
+// chunk of round r, behind a system-scope release.  Before it, in program order of that block:
+// its own chunk's slot reads (their values fed the parameter stores it drained with vmcnt(0)),
+// its counter reset and its chunks_done add.  Every other chunk's closer drained its parameter
+// stores, reset its arrival counter and released BEFORE its chunks_done add, and the finishing
+// block acquires after drawing the last chunks_done ticket.  So every slot read, every
+// parameter store, every counter reset and the global_step store of round r happen-before the
+// round word r+1, hence before any ticket, slot store or counter add of round r+1 -- and
+// before any pull a worker issues after its host poll saw r+1.  Within a round, a slot is
+// written by exactly one ticket holder, and the closer of a chunk reads the R slots only after
+// drawing arrival R-1 (each arrival is behind its writer's drain + release) and acquiring.
+// There is no loop on memory another kernel writes anywhere in this kernel.
+__global__ __launch_bounds__(256) void gps_sync_push_kernel(
+    float* p, float* slots, long long slot_stride, const float* __restrict__ g,
+    const unsigned* __restrict__ dec, unsigned* arrivals,
+    unsigned* chunks_done, unsigned long long* round_word, unsigned long long* step_word,
+    float scale, unsigned R, long long n, unsigned nchunks) {
+  __shared__ unsigned last_s;  // the one LDS word: "this block closes its chunk"
+  if (dec[0] != GPS_JOINED) return;  // STALE / AHEAD / LATE / CONTENDED: touch nothing
+  const unsigned t = dec[1], round = dec[2];
+  if (t >= R) return;
+  const unsigned chunk = blockIdx.x;
+  const long long i = ((long long)chunk * 256 + threadIdx.x) * 4;
+  float* slot = slots + (long long)t * slot_stride;
+  if (i + 3 < n) {
+    *reinterpret_cast<float4*>(slot + i) = *reinterpret_cast<const float4*>(g + i);
+  } else {
+    for (long long k = i; k < n; ++k) slot[k] = g[k];
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // system scope; fence BEFORE the ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned a = __hip_atomic_fetch_add(arrivals + chunk, 1u, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_SYSTEM);
+    last_s = (a == R - 1);
+    if (a == R - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!last_s) return;
+
+  // the R-th arrival of this chunk: s = ((slot0 + slot1) + ...) in ticket order, one apply
+  if (i + 3 < n) {
+    float4 s = *reinterpret_cast<const float4*>(slots + i);
+    for (unsigned k = 1; k < R; ++k) {
+      const float4 v = *reinterpret_cast<const float4*>(slots + (long long)k * slot_stride + i);
+      s.x += v.x;
+      s.y += v.y;
+      s.z += v.z;
+      s.w += v.w;
+    }
+    float4 pv = *reinterpret_cast<const float4*>(p + i);
+    pv.x -= scale * s.x;
+    pv.y -= scale * s.y;
+    pv.z -= scale * s.z;
+    pv.w -= scale * s.w;
+    *reinterpret_cast<float4*>(p + i) = pv;
+  } else {
+    for (long long k = i; k < n; ++k) {
+      float s = slots[k];
+      for (unsigned r = 1; r < R; ++r) s += slots[(long long)r * slot_stride + k];
+      p[k] -= scale * s;
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(arrivals + chunk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned d = __hip_atomic_fetch_add(chunks_done, 1u, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_SYSTEM);
+    if (d == nchunks - 1) {  // the last chunk of the round: finish it
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+      __hip_atomic_store(chunks_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(step_word, (unsigned long long)round + 1, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store(round_word, ((unsigned long long)round + 1) << 32, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
 }  // namespace gps
+
+void gps_sync_join_launch(unsigned long long* round_word, unsigned local_step, unsigned R,
+                          unsigned* dec, const float* extra, int nextra, hipStream_t s) {
+  if (nextra < 0 || nextra > 14) throw std::runtime_error("gpu_ps: at most 14 extra words");
+  hipLaunchKernelGGL(gps::gps_sync_join_kernel, dim3(1), dim3(64), 0, s, round_word, local_step,
+                     R, dec, extra, nextra);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+void gps_sync_push_launch(float* p, float* slots, long long slot_stride, const float* g,
+                          const unsigned* dec, unsigned* arrivals, unsigned* chunks_done,
+                          unsigned long long* round_word, unsigned long long* step_word, float lr,
+                          unsigned R, long long n, hipStream_t s) {
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
+       reinterpret_cast<uintptr_t>(slots)) & 15 || (slot_stride & 3))
+    throw std::runtime_error("gpu_ps: buffers must be 16-byte aligned");
+  if (R < 1 || slot_stride < n) throw std::runtime_error("gpu_ps: bad sync slot layout");
+  const long long blocks = (n + 1023) / 1024;
+  hipLaunchKernelGGL(gps::gps_sync_push_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, slots,
+                     slot_stride, g, dec, arrivals, chunks_done, round_word, step_word,
+                     lr / (float)R, R, n, (unsigned)blocks);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
 
 void gps_pull_launch(float* dst, const float* src, long long n, hipStream_t s) {
   if ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15)

@@ -199,7 +199,8 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_string("ps_device", "cpu",
                   "cpu: variables on the TCP parameter server (the reference) | gpu: variables "
                   "in one GPU-resident store on the chief worker's GPU, IPC-mapped by every "
-                  "worker (pull / apply / global_step over xGMI; async PS only)", fv)
+                  "worker (pull / apply / global_step over xGMI; with --sync_replicas the "
+                  "rounds run on the device too: gradient slots, one apply of the mean)", fv)
     DEFINE_string("cpu_affinity", "numa",
                   "async PS: numa = the ps tasks on GPU 0's NUMA node (--numa_node overrides), "
                   "8 cores each; worker i on 2 cores of its OWN GPU's node, after the ps tasks' "
@@ -225,7 +226,10 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_boolean("sync_replicas", False,
                    "ps_async strategy: aggregate each step's gradients over "
                    "--replicas_to_aggregate workers on the ps before ONE apply "
-                   "(tf.train.SyncReplicasOptimizer); stale gradients are dropped", fv)
+                   "(tf.train.SyncReplicasOptimizer); stale gradients are dropped.  Works "
+                   "with --ps_device cpu (accumulators on the TCP ps) and --ps_device gpu "
+                   "(ticketed gradient slots in the GPU store; a timed-out push is not "
+                   "withdrawn there)", fv)
     DEFINE_integer("replicas_to_aggregate", 0,
                    "--sync_replicas: gradients averaged per step (0 = --num_workers; fewer "
                    "than --num_workers makes the slowest workers backups)", fv)

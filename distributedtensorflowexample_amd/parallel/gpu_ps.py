@@ -22,6 +22,13 @@ non-zero instead of training on a stale mapping.  Checkpoint / restore / readine
 write the GPU store (``read_all`` / ``assign`` / ``uninitialized``), so the Supervisor and
 Saver work unchanged.
 
+``--sync_replicas`` (``sync_replicas = R >= 1``): the allocation also holds a sync control
+region and R gradient slots, and a step is pull, compute, :meth:`GpuPSStore.sync_push_flat`
+-- TF's ``SyncReplicasOptimizer`` on the device: a ticket of the open round, the gradient into
+the ticket's slot, the mean of the R slots applied ONCE by the last arrival of each 1024-float
+chunk, ``global_step`` advanced by the block that finishes the round.  No kernel waits on
+another process; the wait for the round to close is a host poll (``parallel/gpu_ps_sync.py``).
+
 Internal layout: the flat MLP buffer of ``ops/mlp_step.py`` (W1 stored [out, in]); TF layouts
 are converted at the ``assign`` / ``pull`` / ``read_all`` boundary.
 """
@@ -34,6 +41,7 @@ import torch
 
 from ..ops import mlp_step
 from ..ops._ext import hip, stream_handle
+from . import gpu_ps_sync
 from .ps import PSVariableStore
 
 HANDLE = "gpu_ps/ipc_handle"
@@ -65,11 +73,16 @@ class GpuPSStore:
 
     STEP = "global/global_step"
 
-    def __init__(self, ps_addresses, device, num_workers, setter=None, connect_timeout=120.0):
+    def __init__(self, ps_addresses, device, num_workers, setter=None, connect_timeout=120.0,
+                 sync_replicas=0):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("GpuPSStore needs a GPU device")
         self.num_workers = int(num_workers)
+        self.sync_replicas = int(sync_replicas)
+        if self.sync_replicas < 0:
+            raise ValueError("gpu_ps: sync_replicas must be >= 0")
+        self._rounds = None
         nbytes = hip().GpuParamStore.handle_size()
         self._hwords = nbytes // 4
         self.ctl = PSVariableStore(ps_addresses, [(HANDLE, (self._hwords,), "float32"),
@@ -87,7 +100,7 @@ class GpuPSStore:
     def create(self):
         """Chief: allocate the store on this GPU and publish its IPC handle."""
         self.ctl.create()
-        self._st = hip().GpuParamStore(self.device.index or 0, self.n, True)
+        self._st = self._new_store(True)
         self._owner = True
         h = np.frombuffer(self._st.handle(), dtype=np.float32).copy()
         self.ctl.assign({DETACHED: 0})
@@ -112,9 +125,17 @@ class GpuPSStore:
                 raise TimeoutError("gpu_ps: the chief never published the store")
             time.sleep(poll)
         self.generation = self.ctl.read_int(GENERATION)
-        self._st = hip().GpuParamStore(self.device.index or 0, self.n, False)
-        self._st.open(h)
+        self._st = self._new_store(False)
+        self._st.open(h)  # raises if the chief's store has another sync_replicas
         return self
+
+    def _new_store(self, owner):
+        if not self.sync_replicas:  # the async store: exactly the allocation it always was
+            return hip().GpuParamStore(self.device.index or 0, self.n, owner)
+        st = hip().GpuParamStore(self.device.index or 0, self.n, owner, self.sync_replicas)
+        self._rounds = gpu_ps_sync.SyncRounds(st, self.sync_replicas,
+                                              stream=lambda: stream_handle(self.device))
+        return st
 
     def check_generation(self):
         """Non-chief: raise if the chief re-created the store since ``lookup`` (its process
@@ -147,8 +168,13 @@ class GpuPSStore:
             self._st.write(self._host.data_ptr(), 0, self.n * 4)
         if self.STEP in values:
             s = int(torch.as_tensor(values[self.STEP]).item())
-            cur = self._ctrl(STEP_SLOT, 0)
-            self._ctrl(STEP_SLOT, s - cur)
+            if self.sync_replicas:  # also the round word (step << 32); counters re-armed
+                torch.cuda.synchronize(self.device)
+                self._st.set_step(s)
+                self._rounds.joined_round = None
+            else:
+                cur = self._ctrl(STEP_SLOT, 0)
+                self._ctrl(STEP_SLOT, s - cur)
         if self._ctrl(INIT_SLOT, 0) == 0:
             self._ctrl(INIT_SLOT, 1)
 
@@ -173,18 +199,67 @@ class GpuPSStore:
         self.push_apply_flat(g, lr, use_locking)
         torch.cuda.synchronize(self.device)
 
-    def sync_push(self, *a, **k):
-        raise NotImplementedError("--sync_replicas runs on the TCP parameter server "
-                                  "(--ps_device cpu)")
+    # -- synchronous replicas ---------------------------------------------------
+    def _need_sync(self):
+        if self._rounds is None:
+            raise RuntimeError("gpu_ps: the store was built without sync_replicas "
+                               "(or is not created / looked up yet)")
+        return self._rounds
+
+    def sync_push_flat(self, grad, lr, local_step, timeout_s=60.0, record=None):
+        """One synchronous-replicas step from a flat device gradient: join the round
+        ``local_step`` and push (two launches, one read-back), then poll on the host until the
+        round has closed.  Returns ``(step, applied, record)``: the new global step (the next
+        local step), whether this gradient is part of the applied mean, and the floats of
+        ``record`` (a small f32 device tensor: the step's loss / accuracy) read back in the
+        same copy.  A stale push (the round closed without it) returns ``(current step,
+        False, ...)`` at once; a backup replica's push into a full round waits for the close
+        and returns ``(step, False, ...)``.
+
+        Unlike the TCP parameter server, a push that times out (``TimeoutError`` naming the
+        round and ``k of R``) is NOT withdrawn: its slot may already be counted.  Keep
+        waiting with :meth:`sync_push_wait`; pushing again for the same round is refused."""
+        r = self._need_sync()
+        ptr, k = (record.data_ptr(), record.numel()) if record is not None else (0, 0)
+        return r.push(grad.data_ptr(), lr, local_step, timeout_s, ptr, k)
+
+    @property
+    def sync_polls(self):
+        """Host polls of the round word so far (all rounds)."""
+        return self._rounds.polls if self._rounds is not None else 0
+
+    def sync_push_wait(self, local_step, timeout_s=60.0):
+        """Wait (host poll) until the round ``local_step`` has closed; -> the new global step."""
+        return self._need_sync().wait(local_step, timeout_s)
+
+    def sync_push(self, grads, lr, replicas_to_aggregate, local_step,
+                  step_name="global/global_step", timeout_s=600.0):
+        """``PSVariableStore.sync_push`` on the GPU store: {TF name: tensor} gradients (as
+        ``push_apply`` takes them) -> ``(new_global_step, applied)``.  The store's R is fixed
+        at creation: another ``replicas_to_aggregate`` is a ValueError."""
+        if step_name != self.STEP:
+            raise KeyError(step_name)
+        if int(replicas_to_aggregate) != self.sync_replicas:
+            raise ValueError("gpu_ps: the store aggregates %d replicas per round, not %d"
+                             % (self.sync_replicas, int(replicas_to_aggregate)))
+        self._need_sync()
+        g = _flat_from_tf(grads, torch.zeros(self.n, dtype=torch.float32)).to(self.device)
+        step, applied, _ = self.sync_push_flat(g, lr, local_step, timeout_s)
+        return step, applied
 
     def fetch_add(self, name, delta=1):
         if name != self.STEP:
             raise KeyError(name)
+        if self.sync_replicas and int(delta) != 0:
+            raise RuntimeError("gpu_ps: with sync_replicas the rounds own global_step "
+                               "(assign it; a round advances it)")
         return self._ctrl(STEP_SLOT, delta)
 
     def fetch_add_record(self, record, delta=1):
         """global_step fetch-add that also reads back ``record`` (a small f32 device tensor:
         the step's loss / accuracy) in the same copy -- one host round trip per step."""
+        if self.sync_replicas and int(delta) != 0:
+            raise RuntimeError("gpu_ps: with sync_replicas the rounds own global_step")
         old, vals = self._st.fetch_add_read(STEP_SLOT, int(delta), stream_handle(self.device),
                                             record.data_ptr(), record.numel())
         return int(old), vals

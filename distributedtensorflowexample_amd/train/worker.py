@@ -137,13 +137,21 @@ class Worker:
             if not self.use_fused:
                 raise ValueError("--ps_device gpu needs the reference MLP on a GPU worker and "
                                  "1 <= batch_size <= %d" % mlp_step.MAX_BATCH)
+            # --sync_replicas: the store carries R gradient slots and the round protocol
+            # (parallel/gpu_ps_sync.py); R is fixed for the store's life
+            sync_r = 0
             if bool(getattr(flags, "sync_replicas", False)):
-                raise ValueError("--sync_replicas runs on the TCP parameter server "
-                                 "(--ps_device cpu)")
+                sync_r = (int(getattr(flags, "replicas_to_aggregate", 0) or 0)
+                          or int(flags.num_workers))
+                if not 1 <= sync_r <= int(flags.num_workers):
+                    raise ValueError("--ps_device gpu --sync_replicas needs 1 <= "
+                                     "replicas_to_aggregate <= num_workers, got %d (num_workers "
+                                     "%d)" % (sync_r, int(flags.num_workers)))
             from ..parallel.gpu_ps import GpuPSStore
 
             self.store = GpuPSStore(server.target, self.device, int(flags.num_workers),
-                                    setter=replica_device_setter(len(server.target)))
+                                    setter=replica_device_setter(len(server.target)),
+                                    sync_replicas=sync_r)
         else:
             self.store = PSVariableStore(server.target, [v.spec for v in self.global_vars],
                                          setter=replica_device_setter(len(server.target)),
@@ -405,11 +413,22 @@ class Worker:
                     self.store.pull_into(self.params)
                     batch_x, batch_y = dataset.train.next_batch(self.batch_size)
                     self.compute_device(batch_x, batch_y)
-                    self.store.push_apply_flat(self.grad, self.lr,
-                                               bool(getattr(fl, "use_locking", False)))
-                    # counter_op + the step's loss / accuracy record: one read-back
-                    step, (cost, acc) = self.store.fetch_add_record(
-                        self.ws.stats[self._rec_slot])
+                    if sync:
+                        # SyncReplicasOptimizer on the device: a ticket of round local_step, the
+                        # gradient into the ticket's slot, ONE apply of the mean by the round's
+                        # last arrival, which also advances global_step (no fetch_add here);
+                        # the wait for the round to close is a host poll.  The record comes
+                        # back with the join's decision word: one read-back
+                        step = local_step
+                        local_step, _, (cost, acc) = self.store.sync_push_flat(
+                            self.grad, self.lr, local_step, timeout_s=600.0,
+                            record=self.ws.stats[self._rec_slot])
+                    else:
+                        self.store.push_apply_flat(self.grad, self.lr,
+                                                   bool(getattr(fl, "use_locking", False)))
+                        # counter_op + the step's loss / accuracy record: one read-back
+                        step, (cost, acc) = self.store.fetch_add_record(
+                            self.ws.stats[self._rec_slot])
                     self.summary_writer.add_scalars({"loss": cost, "accuracy": acc}, step)
                     history.append((step, cost, acc))
                     local_steps += 1
@@ -483,4 +502,7 @@ class Worker:
                     break
                 if stop_after_secs is not None and time.time() - t_begin > stop_after_secs:
                     break
+        if self.gpu_ps and sync and local_steps:  # the wait for a round to close is host polls
+            self.log("sync rounds: {:.2f} host polls per round".format(
+                self.store.sync_polls / local_steps))
         return history
