@@ -7,6 +7,11 @@
 //                        u32 chunks_done, u32 R, u32 arrivals[ceil(n / 1024)]
 //   R gradient slots     n f32 each (stride: the parameters' padded size)
 // With sync_slots = 0 the allocation is exactly the async one.
+//
+// With opt_slots = 1 (--optimizer momentum: accum) or 2 (adam: m, v) the allocation ends with
+// that many parameter-sized f32 planes (stride: the parameters' padded size), behind everything
+// above; control word [2] records the count, which is the optimizer kind.  With opt_slots = 0
+// every offset and the extent are unchanged.
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 
@@ -35,18 +40,24 @@ void gps_sync_join_launch(unsigned long long*, unsigned, unsigned, unsigned*, co
                           hipStream_t);
 void gps_sync_push_launch(float*, float*, long long, const float*, const unsigned*, unsigned*,
                           unsigned*, unsigned long long*, unsigned long long*, float, unsigned,
-                          long long, hipStream_t);
+                          long long, int, float*, float*, float, float, float, hipStream_t);
+void gps_apply_opt_launch(float*, float*, float*, const float*, const unsigned long long*, float,
+                          int, float, float, float, long long, hipStream_t);
 
 class GpuParamStore {
  public:
-  static constexpr int kCtrlWords = 32;  // [0] global_step, [1] initialised flag
+  // [0] global_step, [1] initialised flag, [2] opt_slots (the optimizer kind)
+  static constexpr int kCtrlWords = 32;
+  static constexpr int kOptWord = 2;
 
   // owner: allocate + zero; otherwise open(handle) before use
-  GpuParamStore(int device, long long n, bool owner, int sync_slots = 0)
-      : device_(device), n_(n), owner_(owner), sync_slots_(sync_slots) {
+  GpuParamStore(int device, long long n, bool owner, int sync_slots = 0, int opt_slots = 0)
+      : device_(device), n_(n), owner_(owner), sync_slots_(sync_slots), opt_slots_(opt_slots) {
     if (n < 1) throw std::runtime_error("gpu_ps: n must be >= 1");
     if (sync_slots < 0 || sync_slots > kMaxSyncSlots)
       throw std::runtime_error("gpu_ps: sync_slots must be in [0, 1024]");
+    if (opt_slots < 0 || opt_slots > 2)
+      throw std::runtime_error("gpu_ps: opt_slots must be 0 (sgd), 1 (momentum) or 2 (adam)");
     GPS_CHECK(hipSetDevice(device));
     pbytes_ = (n * 4 + 255) / 256 * 256;
     used_ = pbytes_ + kCtrlWords * 8;
@@ -56,10 +67,17 @@ class GpuParamStore {
       slots_off_ = sync_off_ + (kSyncHeader + 4 * nchunks_ + 255) / 256 * 256;
       used_ = slots_off_ + (long long)sync_slots_ * pbytes_;
     }
+    opt_off_ = used_;  // 256-byte aligned with or without the sync region
+    used_ += (long long)opt_slots_ * pbytes_;
     bytes_ = (used_ + (2u << 20) - 1) / (2u << 20) * (2u << 20);
     if (owner) {
       GPS_CHECK(hipExtMallocWithFlags(&base_, bytes_, hipDeviceMallocUncached));
       GPS_CHECK(hipMemset(base_, 0, bytes_));
+      if (opt_slots_ > 0) {
+        const unsigned long long k = (unsigned long long)opt_slots_;
+        GPS_CHECK(hipMemcpy(static_cast<char*>(base_) + pbytes_ + 8 * kOptWord, &k, 8,
+                            hipMemcpyHostToDevice));
+      }
     }
     GPS_CHECK(hipHostMalloc(&host_word_, 64, hipHostMallocDefault));
     GPS_CHECK(hipMalloc(&dev_word_, 64));
@@ -92,6 +110,18 @@ class GpuParamStore {
     std::memcpy(&h, handle.data(), sizeof(h));
     GPS_CHECK(hipSetDevice(device_));
     GPS_CHECK(hipIpcOpenMemHandle(&base_, h, hipIpcMemLazyEnablePeerAccess));
+    {  // the owner's optimizer must be this process's (same planes, same apply kernels)
+      unsigned long long k = 0;
+      GPS_CHECK(hipMemcpy(&k, static_cast<char*>(base_) + pbytes_ + 8 * kOptWord, 8,
+                          hipMemcpyDeviceToHost));
+      if (k != (unsigned long long)opt_slots_) {
+        hipIpcCloseMemHandle(base_);
+        base_ = nullptr;
+        throw std::runtime_error("gpu_ps: the store was created with opt_slots = " +
+                                 std::to_string(k) + ", this process asked for " +
+                                 std::to_string(opt_slots_));
+      }
+    }
     if (sync_slots_ > 0) {  // the owner's R must be this process's (same layout, same mean)
       hipDeviceptr_t rb = nullptr;
       size_t rsize = 0;
@@ -123,6 +153,16 @@ class GpuParamStore {
   void push_apply(uintptr_t g, float lr, bool locking, uintptr_t stream) {
     gps_apply_launch(reinterpret_cast<float*>(base()), reinterpret_cast<const float*>(g), lr, n_,
                      locking, reinterpret_cast<hipStream_t>(stream));
+  }
+
+  // async apply of the store's stateful optimizer (opt_slots = 1: momentum, h0 = mu;
+  // opt_slots = 2: adam, h0 = beta1, h1 = beta2, h2 = epsilon) on the parameters and the slot
+  // planes; adam's t is global_step + 1 as each block reads it
+  void push_apply_opt(uintptr_t g, float lr, float h0, float h1, float h2, uintptr_t stream) {
+    need_opt();
+    gps_apply_opt_launch(reinterpret_cast<float*>(base()), opt_plane(0), opt_plane(1),
+                         reinterpret_cast<const float*>(g), ctrl(), lr, opt_slots_, h0, h1, h2,
+                         n_, reinterpret_cast<hipStream_t>(stream));
   }
 
   // control word `slot` += delta on the device (system-scope atomic); returns the old value
@@ -164,6 +204,12 @@ class GpuParamStore {
     if (k < 0 || k >= sync_slots_) throw std::runtime_error("gpu_ps: bad sync slot");
     return slots_off_ + (long long)k * pbytes_;
   }
+  int opt_slots() const { return opt_slots_; }
+  long long opt_offset(int k) const {
+    need_opt();
+    if (k < 0 || k >= opt_slots_) throw std::runtime_error("gpu_ps: bad optimizer slot");
+    return opt_off_ + (long long)k * pbytes_;
+  }
 
   // global_step = step (init / restore).  On a sync-enabled store the rounds own the counter:
   // the round word becomes (step << 32) and the arrival counters are re-armed.  Not for use
@@ -190,8 +236,9 @@ class GpuParamStore {
   // the R-th arrival of each chunk applies p -= (lr / R) * sum) enqueued back to back, then ONE
   // read-back of the decision word and `nextra` (<= 14) f32 words at device address `extra`.
   // Returns (status, round seen, ticket, [floats]); never waits on another worker.
+  // With a stateful optimizer the closer runs it on the mean (h0, h1, h2 as in push_apply_opt).
   py::tuple sync_begin(uintptr_t g, float lr, long long local_step, uintptr_t stream,
-                       uintptr_t extra, int nextra) {
+                       uintptr_t extra, int nextra, float h0, float h1, float h2) {
     need_sync();
     if (local_step < 0 || local_step > 0xffffffffLL)
       throw std::runtime_error("gpu_ps: local_step out of range");
@@ -202,7 +249,7 @@ class GpuParamStore {
       py::gil_scoped_release nogil;
       std::lock_guard<std::mutex> lock(sync_mu_);
       const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-      enqueue_push(g, lr, local_step, s, extra, nextra);
+      enqueue_push(g, lr, local_step, s, extra, nextra, h0, h1, h2);
       GPS_CHECK(hipMemcpyAsync(sync_host_, sync_dev_, 16 + 4 * nextra, hipMemcpyDeviceToHost, s));
       GPS_CHECK(hipStreamSynchronize(s));
       std::memcpy(dec, sync_host_, 16);
@@ -216,13 +263,14 @@ class GpuParamStore {
   // The two launches of sync_begin alone, no read-back and no stream wait: the decision stays
   // on the device and the next call overwrites it.  For timing the launches (with R = 1 every
   // push closes its round, so pushes of consecutive steps can be queued back to back).
-  void sync_enqueue(uintptr_t g, float lr, long long local_step, uintptr_t stream) {
+  void sync_enqueue(uintptr_t g, float lr, long long local_step, uintptr_t stream, float h0,
+                    float h1, float h2) {
     need_sync();
     if (local_step < 0 || local_step > 0xffffffffLL)
       throw std::runtime_error("gpu_ps: local_step out of range");
     py::gil_scoped_release nogil;
     std::lock_guard<std::mutex> lock(sync_mu_);
-    enqueue_push(g, lr, local_step, reinterpret_cast<hipStream_t>(stream), 0, 0);
+    enqueue_push(g, lr, local_step, reinterpret_cast<hipStream_t>(stream), 0, 0, h0, h1, h2);
   }
 
   // (round, tickets_taken): the round word through the store's 8-byte read (fetch-add of 0)
@@ -300,7 +348,7 @@ class GpuParamStore {
   }
   // join + push on `s` (sync_mu_ held: one decision word per store object)
   void enqueue_push(uintptr_t g, float lr, long long local_step, hipStream_t s, uintptr_t extra,
-                    int nextra) {
+                    int nextra, float h0, float h1, float h2) {
     char* b = static_cast<char*>(base());
     unsigned* d = reinterpret_cast<unsigned*>(sync_dev_);
     gps_sync_join_launch(round_word(), (unsigned)local_step, (unsigned)sync_slots_, d,
@@ -309,7 +357,15 @@ class GpuParamStore {
                          pbytes_ / 4, reinterpret_cast<const float*>(g), d,
                          reinterpret_cast<unsigned*>(b + sync_off_ + kSyncHeader),
                          reinterpret_cast<unsigned*>(b + sync_off_ + 8), round_word(), ctrl(), lr,
-                         (unsigned)sync_slots_, n_, s);
+                         (unsigned)sync_slots_, n_, opt_slots_, opt_plane(0), opt_plane(1), h0,
+                         h1, h2, s);
+  }
+  void need_opt() const {
+    if (opt_slots_ < 1) throw std::runtime_error("gpu_ps: the store has no optimizer slots");
+  }
+  float* opt_plane(int k) const {
+    if (k >= opt_slots_) return nullptr;
+    return reinterpret_cast<float*>(static_cast<char*>(base()) + opt_off_ + (long long)k * pbytes_);
   }
   void need_sync() const {
     if (sync_slots_ < 1) throw std::runtime_error("gpu_ps: the store has no sync slots");
@@ -325,9 +381,9 @@ class GpuParamStore {
   int device_;
   long long n_;
   bool owner_;
-  int sync_slots_ = 0;
+  int sync_slots_ = 0, opt_slots_ = 0;
   long long pbytes_ = 0, bytes_ = 0, used_ = 0;
-  long long nchunks_ = 0, sync_off_ = 0, slots_off_ = 0;
+  long long nchunks_ = 0, sync_off_ = 0, slots_off_ = 0, opt_off_ = 0;
   void* sync_host_ = nullptr;
   void* sync_dev_ = nullptr;
   std::mutex sync_mu_;
@@ -341,8 +397,8 @@ class GpuParamStore {
 
 void register_gpu_ps(py::module_& m) {
   py::class_<dtfx::GpuParamStore>(m, "GpuParamStore")
-      .def(py::init<int, long long, bool, int>(), py::arg("device"), py::arg("n"),
-           py::arg("owner"), py::arg("sync_slots") = 0)
+      .def(py::init<int, long long, bool, int, int>(), py::arg("device"), py::arg("n"),
+           py::arg("owner"), py::arg("sync_slots") = 0, py::arg("opt_slots") = 0)
       .def("handle", &dtfx::GpuParamStore::handle)
       .def_static("handle_size", &dtfx::GpuParamStore::handle_size)
       .def("open", &dtfx::GpuParamStore::open)
@@ -351,6 +407,8 @@ void register_gpu_ps(py::module_& m) {
       .def("pull", &dtfx::GpuParamStore::pull, py::arg("dst"), py::arg("stream"))
       .def("push_apply", &dtfx::GpuParamStore::push_apply, py::arg("g"), py::arg("lr"),
            py::arg("locking"), py::arg("stream"))
+      .def("push_apply_opt", &dtfx::GpuParamStore::push_apply_opt, py::arg("g"), py::arg("lr"),
+           py::arg("h0"), py::arg("h1"), py::arg("h2"), py::arg("stream"))
       .def("fetch_add", &dtfx::GpuParamStore::fetch_add, py::arg("slot"), py::arg("delta"),
            py::arg("stream"))
       .def("fetch_add_read", &dtfx::GpuParamStore::fetch_add_read, py::arg("slot"),
@@ -361,11 +419,15 @@ void register_gpu_ps(py::module_& m) {
       .def("sync_slots", &dtfx::GpuParamStore::sync_slots)
       .def("sync_offset", &dtfx::GpuParamStore::sync_offset)
       .def("slot_offset", &dtfx::GpuParamStore::slot_offset)
+      .def("opt_slots", &dtfx::GpuParamStore::opt_slots)
+      .def("opt_offset", &dtfx::GpuParamStore::opt_offset)
       .def("set_step", &dtfx::GpuParamStore::set_step, py::arg("step"))
       .def("sync_begin", &dtfx::GpuParamStore::sync_begin, py::arg("grad"), py::arg("lr"),
-           py::arg("local_step"), py::arg("stream"), py::arg("extra"), py::arg("nextra"))
+           py::arg("local_step"), py::arg("stream"), py::arg("extra"), py::arg("nextra"),
+           py::arg("h0") = 0.f, py::arg("h1") = 0.f, py::arg("h2") = 0.f)
       .def("sync_enqueue", &dtfx::GpuParamStore::sync_enqueue, py::arg("grad"), py::arg("lr"),
-           py::arg("local_step"), py::arg("stream"))
+           py::arg("local_step"), py::arg("stream"), py::arg("h0") = 0.f, py::arg("h1") = 0.f,
+           py::arg("h2") = 0.f)
       .def("sync_poll", &dtfx::GpuParamStore::sync_poll, py::arg("stream"))
       .def("close", &dtfx::GpuParamStore::close);
 }

@@ -13,6 +13,9 @@
 //   gps_apply_kernel  store -= lr * local gradient        (worker.py:79 ApplyGradientDescent:
 //                     use_locking=False -> plain read-modify-write, lock-free / Hogwild like
 //                     TF's default; use_locking=True -> one f32 atomic add per element)
+//   gps_apply_opt_kernel  --optimizer momentum | adam: the same lock-free read-modify-write
+//                     over the parameters AND the optimizer's slot planes (accum, or m and v),
+//                     which live in the store's allocation behind everything else
 //   gps_fetch_add     store.global_step += delta, old value returned (worker.py:32,141)
 //   gps_sync_join / gps_sync_push   --sync_replicas: ticket of the open round, gradient into the
 //                     ticket's slot; the R-th arrival of a chunk applies the mean (below)
@@ -55,6 +58,98 @@ __global__ __launch_bounds__(256) void gps_apply_kernel(float* __restrict__ p,
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Stateful optimizers (--optimizer momentum | adam): ops/optim.py's formulas (optim.hip's
+// momentum_kernel / adam_kernel) with weight_decay = 0 and no Nesterov, on the store's planes.
+//   momentum  accum = mu * accum + g;  p -= lr * accum                        slot0 = accum
+//   adam      m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * g * g       slot0 = m, slot1 = v
+//             p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// t is not stored: it is global_step + 1 at apply time (a sync round's closer has the round in
+// its decision word; an async block reads the step word once at entry), so a restored
+// global_step restores t.  Under concurrent async workers t is whatever the block read, like
+// every other value in a Hogwild apply.
+enum : int { GPS_SGD = 0, GPS_MOMENTUM = 1, GPS_ADAM = 2 };
+
+// momentum: lr, h0 = mu.  adam: lr = lr / (1 - b1^t), h0 = b1, h1 = b2, h2 = eps,
+// rbc2 = 1 / sqrt(1 - b2^t)
+struct GpsCoef {
+  float lr, h0, h1, h2, rbc2;
+};
+
+template <int OPT>
+__device__ __forceinline__ GpsCoef gps_coef(float lr, float h0, float h1, float h2,
+                                            unsigned long long t) {
+  GpsCoef c = {lr, h0, h1, h2, 1.f};
+  if (OPT == GPS_ADAM) {
+    const float tf = (float)t;
+    c.lr = lr / (1.f - powf(h0, tf));
+    c.rbc2 = rsqrtf(1.f - powf(h1, tf));
+  }
+  return c;
+}
+
+template <int OPT>
+__device__ __forceinline__ void gps_update(float& p, float g, float& s0, float& s1,
+                                           const GpsCoef& c) {
+  if (OPT == GPS_MOMENTUM) {
+    s0 = c.h0 * s0 + g;
+    p -= c.lr * s0;
+  } else {
+    s0 = c.h0 * s0 + (1.f - c.h0) * g;
+    s1 = c.h1 * s1 + (1.f - c.h1) * g * g;
+    p -= c.lr * s0 / (sqrtf(s1) * c.rbc2 + c.h2);
+  }
+}
+
+// One optimizer step over elements [i, i + 4) (float4) or the scalar tail [i, n) of a chunk:
+// parameters and slot planes read, updated and stored.  `grad(k)` is element k's gradient.
+template <int OPT, class Grad4, class Grad1>
+__device__ __forceinline__ void gps_step_chunk(float* __restrict__ p, float* __restrict__ s0,
+                                               float* __restrict__ s1, long long i, long long n,
+                                               const GpsCoef& c, Grad4 grad4, Grad1 grad1) {
+  if (i + 3 < n) {
+    const float4 gv = grad4(i);
+    float4 pv = *reinterpret_cast<const float4*>(p + i);
+    float4 av = *reinterpret_cast<const float4*>(s0 + i);
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (OPT == GPS_ADAM) bv = *reinterpret_cast<const float4*>(s1 + i);
+    gps_update<OPT>(pv.x, gv.x, av.x, bv.x, c);
+    gps_update<OPT>(pv.y, gv.y, av.y, bv.y, c);
+    gps_update<OPT>(pv.z, gv.z, av.z, bv.z, c);
+    gps_update<OPT>(pv.w, gv.w, av.w, bv.w, c);
+    *reinterpret_cast<float4*>(s0 + i) = av;
+    if (OPT == GPS_ADAM) *reinterpret_cast<float4*>(s1 + i) = bv;
+    *reinterpret_cast<float4*>(p + i) = pv;
+  } else {
+    for (long long k = i; k < n; ++k) {
+      float pp = p[k], a = s0[k], b = 0.f;
+      if (OPT == GPS_ADAM) b = s1[k];
+      gps_update<OPT>(pp, grad1(k), a, b, c);
+      s0[k] = a;
+      if (OPT == GPS_ADAM) s1[k] = b;
+      p[k] = pp;
+    }
+  }
+}
+
+// Async (Hogwild) apply of a stateful optimizer: gps_apply_kernel<false>'s shape with the slot
+// planes next to the parameters.  The store is uncached memory, so p, s0 and s1 are read and
+// written in HBM directly; g is the worker's own gradient.
+template <int OPT>
+__global__ __launch_bounds__(256) void gps_apply_opt_kernel(
+    float* __restrict__ p, float* __restrict__ s0, float* __restrict__ s1,
+    const float* __restrict__ g, const unsigned long long* step_word, float lr, float h0,
+    float h1, float h2, long long n) {
+  unsigned long long t = 1;
+  if (OPT == GPS_ADAM)  // read once per block, at entry
+    t = __hip_atomic_load(step_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + 1;
+  const GpsCoef c = gps_coef<OPT>(lr, h0, h1, h2, t);
+  const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  gps_step_chunk<OPT>(
+      p, s0, s1, i, n, c, [&](long long k) { return *reinterpret_cast<const float4*>(g + k); },
+      [&](long long k) { return g[k]; });
+}
+
 // out[0] = old counter value; out[1 ..] = `nextra` f32 words copied from `extra` (the
 // worker's loss / accuracy record of the step), so one read-back serves both
 __global__ void gps_fetch_add_kernel(unsigned long long* ctr, long long delta,
@@ -76,7 +171,7 @@ __global__ void gps_fetch_add_kernel(unsigned long long* ctr, long long delta,
 // Sync control region (after the control block; layout in gpu_ps.cpp):
 //   u64 round word  (round << 32) | tickets_taken      u32 chunks_done      u32 R
 //   u32 arrivals[ceil(n / 1024)]
-// followed by R gradient slots of n f32 each.
+// followed by R gradient slots of n f32 each, then the optimizer's slot planes (0, 1 or 2).
 
 enum : unsigned { GPS_JOINED = 0, GPS_STALE = 1, GPS_AHEAD = 2, GPS_LATE = 3, GPS_CONTENDED = 4 };
 constexpr int kJoinRetries = 1 << 16;
@@ -133,15 +228,28 @@ __global__ void gps_sync_join_kernel(unsigned long long* round_word, unsigned lo
 // written by exactly one ticket holder, and the closer of a chunk reads the R slots only after
 // drawing arrival R-1 (each arrival is behind its writer's drain + release) and acquiring.
 // There is no loop on memory another kernel writes anywhere in this kernel.
+//
+// The optimizer's slot planes (OPT = momentum: accum; adam: m, v) are read and written ONLY by a
+// chunk's closer, over that chunk's elements, and every such store is issued before the same
+// vmcnt(0) drain, counter reset and release that cover the parameter stores.  So the argument
+// above holds for them word for word: the slot-plane stores of round r happen-before the round
+// word r+1, hence before the closer of the same chunk in round r+1 reads them.  OPT = sgd is
+// the arithmetic p -= (lr / R) * s it always was; the others form gbar = s * (1 / R) (1 / R
+// rounded to f32 on the host) and run the optimizer on gbar with t = round + 1.
+template <int OPT>
 __global__ __launch_bounds__(256) void gps_sync_push_kernel(
     float* p, float* slots, long long slot_stride, const float* __restrict__ g,
     const unsigned* __restrict__ dec, unsigned* arrivals,
     unsigned* chunks_done, unsigned long long* round_word, unsigned long long* step_word,
-    float scale, unsigned R, long long n, unsigned nchunks) {
+    float scale, unsigned R, long long n, unsigned nchunks, float* opt0, float* opt1, float lr,
+    float h0, float h1, float h2) {
   __shared__ unsigned last_s;  // the one LDS word: "this block closes its chunk"
   if (dec[0] != GPS_JOINED) return;  // STALE / AHEAD / LATE / CONTENDED: touch nothing
   const unsigned t = dec[1], round = dec[2];
   if (t >= R) return;
+  // the optimizer's per-step scalars depend on the decision word alone: formed here, ahead of
+  // the chain of memory round trips below, by every block (only a closer uses them)
+  const GpsCoef c = gps_coef<OPT>(lr, h0, h1, h2, (unsigned long long)round + 1);
   const unsigned chunk = blockIdx.x;
   const long long i = ((long long)chunk * 256 + threadIdx.x) * 4;
   float* slot = slots + (long long)t * slot_stride;
@@ -167,7 +275,27 @@ __global__ __launch_bounds__(256) void gps_sync_push_kernel(
   if (!last_s) return;
 
   // the R-th arrival of this chunk: s = ((slot0 + slot1) + ...) in ticket order, one apply
-  if (i + 3 < n) {
+  if (OPT != GPS_SGD) {  // `scale` is 1 / R here: the optimizer runs on the mean gradient
+    gps_step_chunk<OPT>(
+        p, opt0, opt1, i, n, c,
+        [&](long long e) {
+          float4 s = *reinterpret_cast<const float4*>(slots + e);
+          for (unsigned k = 1; k < R; ++k) {
+            const float4 v =
+                *reinterpret_cast<const float4*>(slots + (long long)k * slot_stride + e);
+            s.x += v.x;
+            s.y += v.y;
+            s.z += v.z;
+            s.w += v.w;
+          }
+          return make_float4(s.x * scale, s.y * scale, s.z * scale, s.w * scale);
+        },
+        [&](long long e) {
+          float s = slots[e];
+          for (unsigned r = 1; r < R; ++r) s += slots[(long long)r * slot_stride + e];
+          return s * scale;
+        });
+  } else if (i + 3 < n) {
     float4 s = *reinterpret_cast<const float4*>(slots + i);
     for (unsigned k = 1; k < R; ++k) {
       const float4 v = *reinterpret_cast<const float4*>(slots + (long long)k * slot_stride + i);
@@ -223,15 +351,48 @@ void gps_sync_join_launch(unsigned long long* round_word, unsigned local_step, u
 void gps_sync_push_launch(float* p, float* slots, long long slot_stride, const float* g,
                           const unsigned* dec, unsigned* arrivals, unsigned* chunks_done,
                           unsigned long long* round_word, unsigned long long* step_word, float lr,
-                          unsigned R, long long n, hipStream_t s) {
+                          unsigned R, long long n, int opt, float* opt0, float* opt1, float h0,
+                          float h1, float h2, hipStream_t s) {
   if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
-       reinterpret_cast<uintptr_t>(slots)) & 15 || (slot_stride & 3))
+       reinterpret_cast<uintptr_t>(slots) | reinterpret_cast<uintptr_t>(opt0) |
+       reinterpret_cast<uintptr_t>(opt1)) & 15 || (slot_stride & 3))
     throw std::runtime_error("gpu_ps: buffers must be 16-byte aligned");
   if (R < 1 || slot_stride < n) throw std::runtime_error("gpu_ps: bad sync slot layout");
+  if (opt < gps::GPS_SGD || opt > gps::GPS_ADAM || (opt >= gps::GPS_MOMENTUM && !opt0) ||
+      (opt == gps::GPS_ADAM && !opt1))
+    throw std::runtime_error("gpu_ps: bad optimizer kind / slot planes");
   const long long blocks = (n + 1023) / 1024;
-  hipLaunchKernelGGL(gps::gps_sync_push_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, slots,
-                     slot_stride, g, dec, arrivals, chunks_done, round_word, step_word,
-                     lr / (float)R, R, n, (unsigned)blocks);
+  const dim3 grid((unsigned)blocks), block(256);
+  // sgd: p -= (lr / R) * s.  Otherwise the closer scales s by 1 / R, rounded to f32 here, once
+  const float scale = opt == gps::GPS_SGD ? lr / (float)R : 1.f / (float)R;
+#define GPS_SYNC_PUSH(OPT)                                                                      \
+  hipLaunchKernelGGL(gps::gps_sync_push_kernel<OPT>, grid, block, 0, s, p, slots, slot_stride,  \
+                     g, dec, arrivals, chunks_done, round_word, step_word, scale, R, n,         \
+                     (unsigned)blocks, opt0, opt1, lr, h0, h1, h2)
+  if (opt == gps::GPS_SGD) GPS_SYNC_PUSH(gps::GPS_SGD);
+  else if (opt == gps::GPS_MOMENTUM) GPS_SYNC_PUSH(gps::GPS_MOMENTUM);
+  else GPS_SYNC_PUSH(gps::GPS_ADAM);
+#undef GPS_SYNC_PUSH
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// async apply of a stateful optimizer: opt = 1 momentum (h0 = mu), 2 adam (h0 = b1, h1 = b2,
+// h2 = eps); s0 / s1 the slot planes
+void gps_apply_opt_launch(float* p, float* s0, float* s1, const float* g,
+                          const unsigned long long* step_word, float lr, int opt, float h0,
+                          float h1, float h2, long long n, hipStream_t s) {
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) |
+       reinterpret_cast<uintptr_t>(s0) | reinterpret_cast<uintptr_t>(s1)) & 15)
+    throw std::runtime_error("gpu_ps: buffers must be 16-byte aligned");
+  if ((opt != gps::GPS_MOMENTUM && opt != gps::GPS_ADAM) || !s0 || (opt == gps::GPS_ADAM && !s1))
+    throw std::runtime_error("gpu_ps: bad optimizer kind / slot planes");
+  const long long blocks = (n + 1023) / 1024;
+  if (opt == gps::GPS_MOMENTUM)
+    hipLaunchKernelGGL(gps::gps_apply_opt_kernel<gps::GPS_MOMENTUM>, dim3((unsigned)blocks),
+                       dim3(256), 0, s, p, s0, s1, g, step_word, lr, h0, h1, h2, n);
+  else
+    hipLaunchKernelGGL(gps::gps_apply_opt_kernel<gps::GPS_ADAM>, dim3((unsigned)blocks),
+                       dim3(256), 0, s, p, s0, s1, g, step_word, lr, h0, h1, h2, n);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

@@ -201,6 +201,16 @@ def define_reference_flags(flag_values=FLAGS):
                   "in one GPU-resident store on the chief worker's GPU, IPC-mapped by every "
                   "worker (pull / apply / global_step over xGMI; with --sync_replicas the "
                   "rounds run on the device too: gradient slots, one apply of the mean)", fv)
+    DEFINE_string("optimizer", "sgd",
+                  "ps_async strategy: sgd (GradientDescentOptimizer, the reference) | momentum | "
+                  "adam (tf.train.MomentumOptimizer / AdamOptimizer).  momentum and adam need "
+                  "--ps_device gpu: their slot variables live in the GPU store next to the "
+                  "variables, the store's kernels update them (async and --sync_replicas) and "
+                  "checkpoints carry them; not with --use_locking", fv)
+    DEFINE_float("momentum", 0.9, "--optimizer momentum: the momentum", fv)
+    DEFINE_float("adam_beta1", 0.9, "--optimizer adam: beta1", fv)
+    DEFINE_float("adam_beta2", 0.999, "--optimizer adam: beta2", fv)
+    DEFINE_float("adam_epsilon", 1e-8, "--optimizer adam: epsilon", fv)
     DEFINE_string("cpu_affinity", "numa",
                   "async PS: numa = the ps tasks on GPU 0's NUMA node (--numa_node overrides), "
                   "8 cores each; worker i on 2 cores of its OWN GPU's node, after the ps tasks' "

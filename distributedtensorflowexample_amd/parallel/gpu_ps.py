@@ -29,6 +29,13 @@ the ticket's slot, the mean of the R slots applied ONCE by the last arrival of e
 chunk, ``global_step`` advanced by the block that finishes the round.  No kernel waits on
 another process; the wait for the round to close is a host poll (``parallel/gpu_ps_sync.py``).
 
+``optimizer="momentum" | "adam"`` (``--optimizer``): the allocation ends with the optimizer's
+slot planes (``parallel/gpu_ps_optim.py``), one parameter-sized plane per slot, and the store's
+apply kernels update them -- in the async apply and in a sync round's closer.  The slots are
+variables like the others: ``global/dense/kernel/Momentum``, ``.../Adam``, ``.../Adam_1`` in
+``uninitialized`` / ``assign`` / ``pull`` / ``read_all``, in TF layout (a kernel's slot is
+transposed exactly as the kernel is).  Adam's ``t`` is ``global_step + 1`` at apply time.
+
 Internal layout: the flat MLP buffer of ``ops/mlp_step.py`` (W1 stored [out, in]); TF layouts
 are converted at the ``assign`` / ``pull`` / ``read_all`` boundary.
 """
@@ -41,7 +48,7 @@ import torch
 
 from ..ops import mlp_step
 from ..ops._ext import hip, stream_handle
-from . import gpu_ps_sync
+from . import gpu_ps_optim, gpu_ps_sync
 from .ps import PSVariableStore
 
 HANDLE = "gpu_ps/ipc_handle"
@@ -50,19 +57,24 @@ GENERATION = "gpu_ps/generation"
 STEP_SLOT, INIT_SLOT = 0, 1
 
 
-def _flat_from_tf(values, out):
+VAR_NAMES = ("global/dense/kernel", "global/dense/bias", "global/dense_1/kernel",
+             "global/dense_1/bias")
+
+
+def _flat_from_tf(values, out, names=VAR_NAMES):
     W1t, b1, W2t, b2 = mlp_step.unflatten(out)
-    W1t.copy_(torch.as_tensor(values["global/dense/kernel"]).t())
-    b1.copy_(torch.as_tensor(values["global/dense/bias"]))
-    W2t.copy_(torch.as_tensor(values["global/dense_1/kernel"]).t())
-    b2.copy_(torch.as_tensor(values["global/dense_1/bias"]))
+    k1, c1, k2, c2 = names
+    W1t.copy_(torch.as_tensor(values[k1]).t())
+    b1.copy_(torch.as_tensor(values[c1]))
+    W2t.copy_(torch.as_tensor(values[k2]).t())
+    b2.copy_(torch.as_tensor(values[c2]))
     return out
 
 
-def _tf_from_flat(p):
+def _tf_from_flat(p, names=VAR_NAMES):
     W1t, b1, W2t, b2 = mlp_step.unflatten(p)
-    return {"global/dense/kernel": W1t.t().contiguous(), "global/dense/bias": b1.clone(),
-            "global/dense_1/kernel": W2t.t().contiguous(), "global/dense_1/bias": b2.clone()}
+    k1, c1, k2, c2 = names
+    return {k1: W1t.t().contiguous(), c1: b1.clone(), k2: W2t.t().contiguous(), c2: b2.clone()}
 
 
 class GpuPSStore:
@@ -74,7 +86,9 @@ class GpuPSStore:
     STEP = "global/global_step"
 
     def __init__(self, ps_addresses, device, num_workers, setter=None, connect_timeout=120.0,
-                 sync_replicas=0):
+                 sync_replicas=0, optimizer="sgd", momentum=gpu_ps_optim.DEFAULTS["momentum"],
+                 beta1=gpu_ps_optim.DEFAULTS["beta1"], beta2=gpu_ps_optim.DEFAULTS["beta2"],
+                 epsilon=gpu_ps_optim.DEFAULTS["epsilon"]):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("GpuPSStore needs a GPU device")
@@ -83,6 +97,10 @@ class GpuPSStore:
         if self.sync_replicas < 0:
             raise ValueError("gpu_ps: sync_replicas must be >= 0")
         self._rounds = None
+        # the optimizer's slot planes: [[TF names of plane k]], and the kernels' hyper words
+        self.optimizer = gpu_ps_optim.check_kind(optimizer)
+        self.slot_names = gpu_ps_optim.slot_names(self.optimizer, VAR_NAMES)
+        self._hyper = gpu_ps_optim.hyper_args(self.optimizer, momentum, beta1, beta2, epsilon)
         nbytes = hip().GpuParamStore.handle_size()
         self._hwords = nbytes // 4
         self.ctl = PSVariableStore(ps_addresses, [(HANDLE, (self._hwords,), "float32"),
@@ -130,11 +148,17 @@ class GpuPSStore:
         return self
 
     def _new_store(self, owner):
-        if not self.sync_replicas:  # the async store: exactly the allocation it always was
+        if not self.sync_replicas and not self.slot_names:
+            # the async sgd store: exactly the allocation it always was
             return hip().GpuParamStore(self.device.index or 0, self.n, owner)
-        st = hip().GpuParamStore(self.device.index or 0, self.n, owner, self.sync_replicas)
-        self._rounds = gpu_ps_sync.SyncRounds(st, self.sync_replicas,
-                                              stream=lambda: stream_handle(self.device))
+        args = (self.device.index or 0, self.n, owner, self.sync_replicas)
+        if self.slot_names:  # the planes behind everything else
+            args += (len(self.slot_names),)
+        st = hip().GpuParamStore(*args)
+        if self.sync_replicas:
+            self._rounds = gpu_ps_sync.SyncRounds(st, self.sync_replicas,
+                                                  stream=lambda: stream_handle(self.device),
+                                                  hyper=self._hyper)
         return st
 
     def check_generation(self):
@@ -153,19 +177,29 @@ class GpuPSStore:
     def uninitialized(self):
         """report_uninitialized_variables: every variable until the first assign."""
         if self._st is None or self._ctrl(INIT_SLOT, 0) == 0:
-            return ["global/dense/kernel", "global/dense/bias", "global/dense_1/kernel",
-                    "global/dense_1/bias", self.STEP]
+            return (list(VAR_NAMES) + [self.STEP]
+                    + [name for plane in self.slot_names for name in plane])
         return []
 
     def assign(self, values):
         """Init / restore: {TF name: tensor/array/int}; the float variables are assigned
-        together (all four are required), global_step alone is allowed."""
-        floats = [k for k in values if k != self.STEP]
+        together (all four are required), so are the optimizer's slot variables (every slot
+        of every variable), global_step alone is allowed."""
+        slots = [name for plane in self.slot_names for name in plane]
+        given = [k for k in values if k in slots]
+        floats = [k for k in values if k != self.STEP and k not in slots]
         if floats:
             if len(floats) != 4:
                 raise ValueError("gpu_ps: assign all four float variables together")
             _flat_from_tf(values, self._host)
             self._st.write(self._host.data_ptr(), 0, self.n * 4)
+        if given:
+            if len(given) != len(slots):
+                raise ValueError("gpu_ps: assign the %s optimizer's %d slot variables together"
+                                 % (self.optimizer, len(slots)))
+            for k, plane in enumerate(self.slot_names):
+                _flat_from_tf(values, self._host, plane)
+                self._st.write(self._host.data_ptr(), self._st.opt_offset(k), self.n * 4)
         if self.STEP in values:
             s = int(torch.as_tensor(values[self.STEP]).item())
             if self.sync_replicas:  # also the round word (step << 32); counters re-armed
@@ -184,14 +218,28 @@ class GpuPSStore:
         self._st.pull(dst.data_ptr(), stream_handle(self.device))
 
     def push_apply_flat(self, grad, lr, use_locking=False):
-        """ApplyGradientDescent on the store from a flat device gradient (stream-ordered)."""
+        """ApplyGradientDescent (or the store's ApplyMomentum / ApplyAdam, slots included) on
+        the store from a flat device gradient (stream-ordered)."""
+        if self.slot_names:
+            if use_locking:
+                raise ValueError("gpu_ps: use_locking needs the sgd optimizer")
+            self._st.push_apply_opt(grad.data_ptr(), float(lr), *self._hyper,
+                                    stream_handle(self.device))
+            return
         self._st.push_apply(grad.data_ptr(), float(lr), bool(use_locking),
                             stream_handle(self.device))
 
     def pull(self, names=None):
+        """{TF name: CPU tensor} of the variables and the optimizer's slots (or of ``names``):
+        one host read per plane, as many as ``names`` needs."""
         host = torch.empty(self.n, dtype=torch.float32, pin_memory=True)  # saver thread too
-        self._st.read(host.data_ptr(), 0, self.n * 4)
-        v = _tf_from_flat(host)
+        planes = [(0, VAR_NAMES)] + [(self._st.opt_offset(k), plane)
+                                     for k, plane in enumerate(self.slot_names)]
+        v = {}
+        for off, plane in planes:
+            if names is None or any(k in plane for k in names):
+                self._st.read(host.data_ptr(), off, self.n * 4)
+                v.update(_tf_from_flat(host, plane))
         return {k: v[k] for k in (names or v)}
 
     def push_apply(self, grads, lr, use_locking=False):

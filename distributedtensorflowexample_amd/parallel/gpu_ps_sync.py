@@ -4,7 +4,8 @@ The device side (``csrc/kernels/gpu_ps.hip``: ``gps_sync_join_kernel`` /
 ``gps_sync_push_kernel``) never waits on another process.  A push takes a ticket of the open
 round on the packed round word ``(round << 32) | tickets_taken``, stores the gradient into the
 ticket's slot and returns; the R-th arrival of a chunk sums the slots in ticket order and
-applies ``p -= (lr / R) * sum``; the block that completes the last chunk advances
+applies ``p -= (lr / R) * sum`` (or, with ``--optimizer momentum | adam``, runs that optimizer on
+the mean and the chunk's slot planes: ``gpu_ps_optim.py``); the block that completes the last chunk advances
 ``global_step`` and publishes the next round word.  Every wait is here, on the host:
 :class:`SyncRounds` polls the round word until the round it joined has closed.
 
@@ -83,9 +84,13 @@ class SyncRounds:
 
     SPIN_POLLS = 64  # polls without yielding the core; later ones yield (sleep(0))
 
-    def __init__(self, st, replicas, stream=lambda: 0, clock=time.monotonic, sleep=time.sleep):
+    def __init__(self, st, replicas, stream=lambda: 0, clock=time.monotonic, sleep=time.sleep,
+                 hyper=()):
         self.st = st
         self.replicas = int(replicas)
+        # a stateful optimizer's hyper-parameter words (gpu_ps_optim.hyper_args), appended to
+        # every sync_begin: the round's closer runs the optimizer on the mean gradient
+        self.hyper = tuple(float(h) for h in hyper)
         self._stream, self._clock, self._sleep = stream, clock, sleep
         self.joined_round = None  # the last round this worker holds (held) a ticket of
         self.polls = 0  # host polls so far (tools/probes/gpu_ps_sync_cost.py)
@@ -101,7 +106,8 @@ class SyncRounds:
                                "(a timed-out push is not withdrawn: wait for it with "
                                "sync_push_wait)" % local_step)
         status, round_, ticket, vals = self.st.sync_begin(
-            int(grad_ptr), float(lr), local_step, self._stream(), int(extra_ptr), int(nextra))
+            int(grad_ptr), float(lr), local_step, self._stream(), int(extra_ptr), int(nextra),
+            *self.hyper)
         status, round_ = int(status), int(round_)
         vals = [float(v) for v in vals]
         if status == STALE:

@@ -30,6 +30,7 @@ import torch
 from .. import variables as vs
 from ..models.dense import make_ps_model
 from ..ops import mlp_step
+from ..parallel import gpu_ps_optim
 from ..parallel.ps import PSVariableStore, replica_device_setter
 from ..utils.summary import FileWriter
 from .saver import FastSaver
@@ -38,18 +39,41 @@ from .supervisor import Supervisor
 D, H, C = mlp_step.D, mlp_step.H, mlp_step.C
 
 
-def build_worker_variables(model, registry, global_scope="global", local_scope="local"):
+def build_worker_variables(model, registry, global_scope="global", local_scope="local",
+                           optimizer="sgd"):
     """worker.py:24-40: the global replica + global_step under ``global`` (on the ps), the
     local replica under ``local`` (this worker's device; never saved).  Returns the
     registry's ``get_vars('global', False)`` -- ps variables and saver var list -- and
-    ``get_vars('global')`` -- the trainable ones gradients are paired with (worker.py:76-77)."""
+    ``get_vars('global')`` -- the trainable ones gradients are paired with (worker.py:76-77).
+
+    ``optimizer`` momentum / adam: its slot variables (``<var>/Momentum``; ``<var>/Adam`` and
+    ``<var>/Adam_1``) are declared last, as TF's ``minimize`` creates them: non-trainable
+    globals, zero-initialised, so ``get_vars('global', False)`` -- hence the init op and the
+    saver's var list -- includes them."""
     with registry.as_default():
         with vs.variable_scope(global_scope):
             model.build_variables()
             vs.create_global_step()
         with vs.variable_scope(local_scope):
             model.build_variables()
-        return vs.get_vars(global_scope, False), vs.get_vars(global_scope)
+        trainable = vs.get_vars(global_scope)
+        with vs.variable_scope(global_scope):
+            for slot in gpu_ps_optim.SLOT_NAMES[gpu_ps_optim.check_kind(optimizer)]:
+                for v in trainable:
+                    vs.get_variable("%s/%s" % (v.local_name, slot), v.shape, trainable=False)
+        return vs.get_vars(global_scope, False), trainable
+
+
+def restricted_assign(assign, names):
+    """The saver's assign callback over its var list only: ``Saver.restore`` hands over every
+    tensor of the checkpoint, and one written by a momentum / Adam run holds slot variables
+    that an sgd run (or another optimizer's) does not have -- TF restores the var list and
+    ignores the rest."""
+    names = list(names)
+
+    def fn(values):
+        return assign({k: values[k] for k in names if k in values})
+    return fn
 
 
 # the reference's names (worker.py:27-31 + tf.layers.dense naming): the sync-DP checkpoints
@@ -108,6 +132,11 @@ class Worker:
         self.server = server
         self.flags = flags
         self.log = log
+        # --optimizer: stateful kinds only on the GPU store, and never locked (refused here,
+        # before any device, server or file is touched)
+        self.optimizer = gpu_ps_optim.validate(getattr(flags, "optimizer", "sgd"),
+                                               getattr(flags, "ps_device", "cpu"),
+                                               bool(getattr(flags, "use_locking", False)))
         if device is None or device == "auto":
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
@@ -121,8 +150,8 @@ class Worker:
                                    getattr(flags, "hidden_units", ""),
                                    getattr(flags, "activation", None))
         self.registry = vs.VariableRegistry()
-        self.global_vars, self.trainable = build_worker_variables(self.model, self.registry,
-                                                                  global_scope)
+        self.global_vars, self.trainable = build_worker_variables(
+            self.model, self.registry, global_scope, optimizer=self.optimizer)
         self.step_name = next(v.name for v in self.global_vars if v.name.endswith("global_step"))
         self.use_fused = (self.model.is_reference_mlp and self.device.type == "cuda"
                           and 1 <= self.batch_size <= mlp_step.MAX_BATCH)
@@ -151,7 +180,7 @@ class Worker:
 
             self.store = GpuPSStore(server.target, self.device, int(flags.num_workers),
                                     setter=replica_device_setter(len(server.target)),
-                                    sync_replicas=sync_r)
+                                    sync_replicas=sync_r, **self._optimizer_kwargs())
         else:
             self.store = PSVariableStore(server.target, [v.spec for v in self.global_vars],
                                          setter=replica_device_setter(len(server.target)),
@@ -183,7 +212,19 @@ class Worker:
         self._test = None  # device-resident test set of the eval op (uploaded once)
         self.summary_writer = FileWriter(flags.logdir + "_%d" % self.task_index)
         # FastSaver over get_vars('global', False) (worker.py:102-103)
-        self.saver = FastSaver({v.name: None for v in self.global_vars}, assign=self.store.assign)
+        # (slot variables included; a checkpoint's other tensors are not restored)
+        names = [v.name for v in self.global_vars]
+        self.saver = FastSaver({k: None for k in names},
+                               assign=restricted_assign(self.store.assign, names))
+
+    def _optimizer_kwargs(self):
+        """--optimizer and its hyper-parameter flags as GpuPSStore's keyword arguments."""
+        d, fl = gpu_ps_optim.DEFAULTS, self.flags
+        return dict(optimizer=self.optimizer,
+                    momentum=float(getattr(fl, "momentum", d["momentum"])),
+                    beta1=float(getattr(fl, "adam_beta1", d["beta1"])),
+                    beta2=float(getattr(fl, "adam_beta2", d["beta2"])),
+                    epsilon=float(getattr(fl, "adam_epsilon", d["epsilon"])))
 
     # -- graph pieces (as ops) ---------------------------------------------
     def init_op(self):
@@ -359,7 +400,7 @@ class Worker:
         from ..utils.graph import reference_mlp_graph
 
         return reference_mlp_graph(self.global_vars, self.trainable, self.task_index,
-                                   learning_rate=self.lr)
+                                   learning_rate=self.lr, optimizer=self.optimizer)
 
     # -- training loop (worker.py:105-159) ------------------------------------
     def learn(self, dataset, max_steps=None, stop_after_secs=None):

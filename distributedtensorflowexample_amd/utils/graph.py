@@ -127,12 +127,23 @@ def graph_event(graph_def, wall_time=None):
     return _key(1, 1) + struct.pack("<d", w) + _bytes_field(4, graph_def)
 
 
+# --optimizer: (scope of the optimizer's nodes, update op, slot names in the op's input order)
+_OPTIMIZER_OPS = {"sgd": ("GradientDescent", "ApplyGradientDescent", ()),
+                  "momentum": ("Momentum", "ApplyMomentum", ("Momentum",)),
+                  "adam": ("Adam", "ApplyAdam", ("Adam", "Adam_1"))}
+
+
 def reference_mlp_graph(global_vars, trainable, task_index=0, batch_size=-1,
-                        learning_rate=0.001):
+                        learning_rate=0.001, optimizer="sgd"):
     """The reference worker's graph (worker.py:8-103) over the registry's variables.
 
-    ``global_vars``: ``get_vars('global', False)`` (ps variables incl. global_step);
-    ``trainable``: ``get_vars('global')`` (the four dense kernels / biases, creation order)."""
+    ``global_vars``: ``get_vars('global', False)`` (ps variables incl. global_step and, for
+    ``optimizer`` momentum / adam, the slot variables); ``trainable``: ``get_vars('global')``
+    (the four dense kernels / biases, creation order).  A stateful optimizer's update nodes
+    are ``ApplyMomentum`` (var, accum, lr, grad, momentum) / ``ApplyAdam`` (var, m, v,
+    beta1_power, beta2_power, lr, beta1, beta2, epsilon, grad) with TF's input order; the
+    beta powers are ``Pow`` nodes over ``global_step + 1``, not variables."""
+    scope, apply_op, slot_names = _OPTIMIZER_OPS[optimizer]
     g = GraphDefBuilder()
     ps = "/job:ps/task:0"
     wdev = "/job:worker/task:%d/gpu:0" % task_index
@@ -171,16 +182,38 @@ def reference_mlp_graph(global_vars, trainable, task_index=0, batch_size=-1,
     loss = g.node("local/Mean", "Mean", [xent], device=wdev)
     # compute_gradients on the local replica, apply_gradients to the GLOBAL variables
     # (worker.py:70-79): one ApplyGradientDescent per (global var, local grad) pair, on the ps
-    lr = g.node("local/GradientDescent/learning_rate", "Const", device=wdev,
-                dtype=("type", "float32"))
+    def const(name):
+        return g.node("local/%s/%s" % (scope, name), "Const", device=wdev,
+                      dtype=("type", "float32"))
+
+    lr = const("learning_rate")
+    hyper = []  # the inputs between the slots and the gradient
+    if optimizer == "momentum":
+        mu = const("momentum")
+    elif optimizer == "adam":
+        b1, b2, eps = const("beta1"), const("beta2"), const("epsilon")
+        t = g.node("local/Adam/t", "Cast", [g.node("local/Adam/add", "AddV2",
+                                                    [step, g.node("local/Adam/one", "Const",
+                                                                  device=ps,
+                                                                  dtype=("type", "int32"))],
+                                                    device=ps)], device=ps)
+        hyper = [g.node("local/Adam/beta1_power", "Pow", [b1, t], device=ps),
+                 g.node("local/Adam/beta2_power", "Pow", [b2, t], device=ps), lr, b1, b2, eps]
     grads = g.node("local/gradients/Fill", "Fill", [loss], device=wdev)
     upd = []
     for v in trainable:
         gn = g.node("local/gradients/%s_grad" % local[v.name].split("/", 1)[1].replace("/", "_"),
                     "Identity", [grads], device=wdev)
-        upd.append(g.node("local/GradientDescent/update_%s/ApplyGradientDescent" % v.name,
-                          "ApplyGradientDescent", [v.name, lr, gn], device=ps))
-    g.node("local/GradientDescent", "NoOp", ["^" + u for u in upd], device=wdev)
+        slots = ["%s/%s" % (v.name, s) for s in slot_names]
+        if optimizer == "sgd":
+            inputs = [v.name, lr, gn]
+        elif optimizer == "momentum":
+            inputs = [v.name] + slots + [lr, gn, mu]
+        else:
+            inputs = [v.name] + slots + hyper + [gn]
+        upd.append(g.node("local/%s/update_%s/%s" % (scope, v.name, apply_op), apply_op, inputs,
+                          device=ps))
+    g.node("local/" + scope, "NoOp", ["^" + u for u in upd], device=wdev)
     # sync_op (worker.py:81-85): local <- global
     asg = [g.node("local/Assign%s" % ("" if i == 0 else "_%d" % i), "Assign",
                   [local[v.name], v.name], device=wdev) for i, v in enumerate(trainable)]

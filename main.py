@@ -52,6 +52,11 @@ def main(argv=None):
         from distributedtensorflowexample_amd.train.eval_job import eval_job
 
         return eval_job(FLAGS)
+    if FLAGS.strategy == "mirrored" and FLAGS.optimizer != "sgd":
+        # --optimizer momentum | adam: the GPU parameter store's (train/worker.py validates the
+        # ps_async combinations); never silently ignored
+        raise SystemExit("--optimizer %s needs --strategy ps_async --ps_device gpu"
+                         % FLAGS.optimizer)
     if FLAGS.strategy == "mirrored" and FLAGS.model != "mlp":
         from distributedtensorflowexample_amd.train.mirrored_mlp import shutdown_mirrored
         from distributedtensorflowexample_amd.train.mirrored_models import train_model_mirrored

@@ -10,7 +10,12 @@ the variables in the GPU store (``--ps_device gpu``) against the TCP parameter s
 (``--ps_device cpu``: the only way before the GPU rounds existed, the baseline), run
 alternately; the GPU-store workers also report their host polls per round.
 
+``--part optim``: device time of one push per optimizer (sgd, momentum, adam; n = 79510):
+the async apply, and the sync push with R = 1 through ``sync_enqueue`` (every push closes its
+round and runs the optimizer), six variants interleaved block by block in one process.
+
     python tools/probes/gpu_ps_sync_cost.py --part push
+    python tools/probes/gpu_ps_sync_cost.py --part optim
     python tools/probes/gpu_ps_sync_cost.py --part cluster --steps 6000 --reps 2
 """
 import argparse
@@ -96,6 +101,69 @@ def part_push(a):
     return 0
 
 
+def part_optim(a):
+    import torch
+
+    from distributedtensorflowexample_amd.ops import hip, mlp_step
+    from distributedtensorflowexample_amd.ops._ext import stream_handle
+    from distributedtensorflowexample_amd.parallel import gpu_ps_optim
+
+    dev = torch.device("cuda:0")
+    n = mlp_step.NPARAM
+    s = stream_handle(dev)
+    g = torch.randn(n, device=dev) * 1e-3
+    stores, blocks = [], {}
+    for kind in gpu_ps_optim.KINDS:
+        k, hyper = gpu_ps_optim.num_slots(kind), gpu_ps_optim.hyper_args(kind)
+        async_st = hip().GpuParamStore(0, n, True, 0, k)
+        sync_st = hip().GpuParamStore(0, n, True, 1, k)
+        stores += [async_st, sync_st]
+        step = [0]
+
+        def async_block(count, st=async_st, hyper=hyper):
+            for _ in range(count):
+                if hyper:
+                    st.push_apply_opt(g.data_ptr(), 0.001, *hyper, s)
+                else:
+                    st.push_apply(g.data_ptr(), 0.001, False, s)
+
+        def sync_block(count, st=sync_st, hyper=hyper, step=step):
+            for _ in range(count):
+                st.sync_enqueue(g.data_ptr(), 0.001, step[0], s, *hyper)
+                step[0] += 1
+
+        blocks["async " + kind] = async_block
+        blocks["sync " + kind] = sync_block
+
+    def timed(fn, k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn(k)
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / k  # us per call
+
+    for fn in blocks.values():
+        timed(fn, a.block)  # warm-up: code load, first launches
+    dev_us = {name: [] for name in blocks}
+    for _ in range(a.blocks):  # interleaved: clocks and neighbours change together for all
+        for name, fn in blocks.items():
+            dev_us[name].append(timed(fn, a.block))
+    for st in stores[1::2]:  # every queued sync push closed its round
+        assert st.sync_poll(s) == ((a.blocks + 1) * a.block, 0)
+
+    def summary(v):
+        v = sorted(v)
+        return {"median_us": round(statistics.median(v), 2), "min_us": round(v[0], 2),
+                "max_us": round(v[-1], 2), "n": len(v)}
+
+    print(json.dumps({"part": "optim", "n": n, "R": 1, "calls_per_block": a.block,
+                      "device_time_per_push": {k: summary(v) for k, v in dev_us.items()}}))
+    for st in stores:
+        st.close()
+    return 0
+
+
 def part_cluster(a):
     from distributedtensorflowexample_amd.launch import launch_ps
 
@@ -139,7 +207,7 @@ def part_cluster(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=["push", "cluster"], required=True)
+    ap.add_argument("--part", choices=["push", "optim", "cluster"], required=True)
     ap.add_argument("--block", type=int, default=200, help="push: calls queued per timed block")
     ap.add_argument("--blocks", type=int, default=20, help="push: timed blocks per variant")
     ap.add_argument("--steps", type=int, default=6000)
@@ -148,7 +216,7 @@ def main():
     ap.add_argument("--base_port", type=int, default=25222)
     ap.add_argument("--timeout", type=float, default=240.0)
     a = ap.parse_args()
-    return part_push(a) if a.part == "push" else part_cluster(a)
+    return {"push": part_push, "optim": part_optim, "cluster": part_cluster}[a.part](a)
 
 
 if __name__ == "__main__":
