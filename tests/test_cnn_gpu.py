@@ -159,7 +159,9 @@ def test_batchnorm_fwd_bwd(gpu):
     assert torch.allclose(db.cpu(), dbr, atol=1e-2, rtol=1e-3)
 
 
-@pytest.mark.parametrize("C", [64, 96, 2048])  # 96: the general (per-element channel) path
+# 96: the fast path with a non-power-of-two channel-group count (M = 252: the grid stride 1536 is
+# a multiple of 12); the general per-element channel loop: tests/test_cnn_layer_kernels_gpu.py
+@pytest.mark.parametrize("C", [64, 96, 2048])
 def test_batchnorm_apply_from_sums(gpu, C):
     """Fused finalize + apply (bn_apply_stats): mean / rstd / running statistics and the output
     match bn_finalize + bn_apply on the CPU; with res_bn the residual (a raw conv output) is
