@@ -40,6 +40,14 @@
 // (profiles/lean_step/: -0.56 us per step, bit-identical results).  mlp_fwdapply_launch /
 // mlp_head2_launch, the data-parallel engines and the opt-in fused flush keep
 // mlp_fwdapply_kernel / mlp_head_kernel.  Measured and not kept there: tile-major z1 slabs.
+// The lean first launch also applies W1 in 16-byte accesses (fwdapply_block<.., A16>,
+// profiles/wide_wt_stores/: -0.21 us per step, bit-identical results): one float4 of p_old,
+// p_new and Wt per live lane on all four waves, the p_old load issued by every lane without a
+// branch, so phase A's vmcnt waits are the exact ones.  Measured and not kept there:
+//   phase B with swapped MFMA operands and one float4 slab store per lane: within the noise;
+//   those slab stores written through (sc1): the boundary to the head shrinks by what the
+//     stores' own drain adds to the launch's tail, no gain per step;
+//   p_new written through as well: slower in the driver-sized run.
 //
 // All MFMA work is v_mfma_f32_16x16x4_f32 (exact f32).  Lane l supplies
 // A[i = l&15][k = l>>4], B[k = l>>4][j = l&15]; C[row = (l>>4)*4 + r][col = l&15].
@@ -1071,8 +1079,14 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(
 // MFMA's vmcnt then leaves pw and the cold xa rows in flight instead of waiting for them.
 // trs (TRACE, NGT > 0, optional): [blocks * 4 waves][2] split stamps -- 0: the first-issued operand
 // class has landed (ORD: factors + x_prev; else the xa rows), 1: unused.
+// A16 (the lean step only, on top of ORD; profiles/wide_wt_stores/): the W1 apply runs on all
+// four waves over items of (hidden row, four adjacent features), 28 per wave -- one float4 of
+// p_old per live lane, requested by every lane of every wave at the pw position (no branch: the
+// first MFMA's vmcnt leaves pw and xa in flight, the apply waits for pw alone), the four
+// partials read back from LDS as one float4 per wave and added in wave order, one float4 store
+// each to p_new and Wt -- instead of waves 0 / 1 moving four dwords at stride D each.
 template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true,
-          bool ORD = false>
+          bool ORD = false, bool A16 = false>
 __device__ __forceinline__ void fwdapply_block(
     const int bid, const float* __restrict__ p_old, float* __restrict__ p_new, float lr,
     const float* __restrict__ x_prev, const float* __restrict__ x, const Bufs& w,
@@ -1080,6 +1094,7 @@ __device__ __forceinline__ void fwdapply_block(
     const MlpXg& xg, unsigned long long* __restrict__ tr,
     unsigned long long* __restrict__ trs = nullptr) {
   static_assert(!ORD || (XW == 0 && KSX == KS3), "load order of the row-quad form");
+  static_assert(!A16 || ORD, "the 16-byte apply belongs to the lean step");
   // stamps per wave: 0 entry, 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab
   // stored; with XW > 0 also 4 local gradient slice ready (exchange starts), 5 two-shot: the
   // owned sums done (first hop), 6 exchange done -- 8 slots per wave then
@@ -1109,7 +1124,9 @@ __device__ __forceinline__ void fwdapply_block(
   constexpr int LW = KWX + 4;  // LDS row pitch (floats)
   __shared__ float Wt[16][LW];
   __shared__ float Kred[!RM && KSP > 1 ? NCG : 1][64][4];  // phase-A K-split partials
-  __shared__ f32x4 red[RM ? 4 * 2 * 64 : 1];               // row-quad form: (wave, accumulator)
+  __shared__ f32x4 red[RM && !A16 ? 4 * 2 * 64 : 1];       // row-quad form: (wave, accumulator)
+  // A16: the four partial tiles as [wave][hidden row][feature]
+  __shared__ __attribute__((aligned(16))) float redw[A16 ? 4 : 1][A16 ? 16 : 1][KWX];
   const int jt = bid / KSX, ks = bid % KSX;
   const int f0 = ks * KWX;
   // phase B's x rows are independent of phase A: requested first, so the whole launch
@@ -1146,8 +1163,17 @@ __device__ __forceinline__ void fwdapply_block(
     float pw[4] = {0.f, 0.f, 0.f, 0.f};
     // (the wave-uniform branch also keeps the loads HERE: issued unconditionally, the compiler
     // sinks them into the apply branch after the barrier -- a serial round trip)
+    // A16: item (hidden row hw, feature quad mw) of this lane; lanes >= IPW repeat the
+    // wave's last item (same addresses, same values), so nothing before the p_new store branches
+    constexpr int MQ = KWX / 4, IPW = 16 * MQ / 4;
+    static_assert(!A16 || (16 * MQ) % 4 == 0, "items per wave");
+    const int item = wave * IPW + (lane < IPW ? lane : IPW - 1);
+    const int hw = item / MQ, mw = item % MQ, jw = jt * 16 + hw;
+    float4 pw4 = {0.f, 0.f, 0.f, 0.f};
     auto load_pw = [&]() {
-      if (wave < 2) {
+      if constexpr (A16) {
+        pw4 = f4(p_old + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
+      } else if (wave < 2) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int j = jt * 16 + q * 4 + i;
@@ -1179,7 +1205,8 @@ __device__ __forceinline__ void fwdapply_block(
       if (trs) {  // loads issued after the first class: ORD pw + xa, else pw + the factors
         unsigned long long* t2 = trs + (size_t)(bid * 4 + wave) * 2;
         constexpr int NLATE = ORD ? RTW * G2 : 2 * NGT;
-        if (wave < 2) trace_stamp_vm<NLATE + 4>(t2, 0);
+        if constexpr (A16) trace_stamp_vm<NLATE + 1>(t2, 0);
+        else if (wave < 2) trace_stamp_vm<NLATE + 4>(t2, 0);
         else trace_stamp_vm<NLATE>(t2, 0);
       }
     }
@@ -1192,6 +1219,29 @@ __device__ __forceinline__ void fwdapply_block(
         a1 = mfma16x16x4(av[u], xv[u].y, a1);
       }
     }
+    if constexpr (A16) {
+      if (lv) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)  // features 2r, 2r + 1 of hidden row 4q + i
+          *reinterpret_cast<float2*>(&redw[wave][q * 4 + i][2 * r]) = float2{a0[i], a1[i]};
+      }
+      __syncthreads();
+      float4 part = *reinterpret_cast<const float4*>(&redw[0][hw][4 * mw]);
+#pragma unroll
+      for (int k = 1; k < 4; ++k) {  // wave order
+        const float4 o = *reinterpret_cast<const float4*>(&redw[k][hw][4 * mw]);
+        part.x += o.x, part.y += o.y, part.z += o.z, part.w += o.w;
+      }
+      const bool live = jw < H;
+      float4 v;
+      v.x = pw4.x - lr * part.x, v.y = pw4.y - lr * part.y;
+      v.z = pw4.z - lr * part.z, v.w = pw4.w - lr * part.w;
+      // (every lane: the LDS store also keeps the pw load above the barrier, where it was issued)
+      if (FWD)  // padded hidden rows contribute exact zeros
+        *reinterpret_cast<float4*>(&Wt[hw][4 * mw]) = live ? v : float4{0.f, 0.f, 0.f, 0.f};
+      if (lane < IPW && live)
+        *reinterpret_cast<float4*>(p_new + OFF_W1 + (size_t)jw * D + f0 + 4 * mw) = v;
+    } else {
     red[(wave * 2 + 0) * 64 + lane] = a0;
     red[(wave * 2 + 1) * 64 + lane] = a1;
     __syncthreads();
@@ -1214,6 +1264,7 @@ __device__ __forceinline__ void fwdapply_block(
         }
       }
     }
+    }  // !A16
   } else {
     // ---- phase A: this wave's 16 x 16 slice of the updated W1 tile (K split sp of KSP) -----
     const int cgp = wave % NCG, sp = wave / NCG;
@@ -1441,7 +1492,7 @@ __device__ __forceinline__ void lean_fwdapply_body(
     unsigned long long* __restrict__ trs) {
   const int B = flags & 511, stats_on = (flags >> 9) & 1, stats_ring = flags >> 10;
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
-  fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true>(
+  fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true>(
       blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{}, tr,
       trs);
 }
@@ -2191,6 +2242,9 @@ static void lean_first_launch(const float* p_old, float* p_new, float lr, const 
                               int B, int stats_on, hipStream_t stream) {
   using namespace mlp;
   const int flags = lean_flags(B, stats_on, stats, stats_ring);
+  // (fwdapply_block<.., A16>: W1 moves as float4s)
+  if ((reinterpret_cast<uintptr_t>(p_old) | reinterpret_cast<uintptr_t>(p_new)) & 15)
+    throw std::runtime_error("fused MLP step: parameter buffers must be 16-byte aligned");
   dim3 grid(HT * KS3 + HT), block(256);
   if ((B + 15) / 16 == 7)
     hipLaunchKernelGGL((mlp_lean_fwdapply_kernel<7, FWD>), grid, block, 0, stream, p_old, p_new,
