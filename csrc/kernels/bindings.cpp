@@ -46,6 +46,20 @@ void mlp_run_pipelined_launch(float*, float*, int, int, float, const float*, con
                               int, float*, int*, float*, int, int, hipStream_t, int);
 void mlp_apply_launch(const float*, float*, float, const float*, float*, int*, float*, int, int,
                       hipStream_t);
+// momentum / adam variants of the lean two-launch step (mlp_step.hip)
+struct MlpOpt {
+  int kind;
+  float *s0, *s1;
+  int* tp;
+  float h0, h1, h2;
+};
+void mlp_lean_fwdapply_opt_launch(const float*, float*, float, const float*, const float*, float*,
+                                  int*, float*, int, int, int, int, const MlpOpt&, hipStream_t);
+void mlp_apply_opt_launch(const float*, float*, float, const float*, float*, int*, float*, int,
+                          int, int, const MlpOpt&, hipStream_t);
+void mlp_run_pipelined_opt_launch(float*, float*, int, int, float, const float*, const int*, int,
+                                  int, int, float*, int*, float*, int, int, hipStream_t, int,
+                                  const MlpOpt&);
 long long mlp_persistent_ll_words();
 int mlp_persistent_blocks();
 int mlp_persistent_trace_steps();
@@ -247,6 +261,62 @@ PYBIND11_MODULE(_hip, m) {
     dtfx::mlp_apply_launch(P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev),
                            P<float>(ws), P<int>(ctr), P<float>(stats), ring, B, S(s));
   });
+  // Momentum / Adam inside the two-launch step.  kind: 1 momentum, 2 adam; s0 / s1: slot planes
+  // (s1: adam only, else 0); tp: the int32[2] step pair; h0..h2: gpu_ps_optim.hyper_args; par:
+  // the index of p_old in the ping-pong pair.
+  m.def("mlp_lean_fwdapply_opt", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                                    uintptr_t x, uintptr_t ws, uintptr_t ctr, uintptr_t stats,
+                                    int ring, int B, int apply, int par, int kind, uintptr_t s0,
+                                    uintptr_t s1, uintptr_t tp, float h0, float h1, float h2,
+                                    uintptr_t s) {
+    dtfx::mlp_lean_fwdapply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<const float>(x),
+        P<float>(ws), P<int>(ctr), P<float>(stats), ring, B, apply, par,
+        dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1, h2}, S(s));
+  }, py::arg("p_old"), py::arg("p_new"), py::arg("lr"), py::arg("x_prev"), py::arg("x"),
+     py::arg("ws"), py::arg("ctr"), py::arg("stats"), py::arg("ring"), py::arg("B"),
+     py::arg("apply"), py::arg("par"), py::arg("kind"), py::arg("s0"), py::arg("s1"),
+     py::arg("tp"), py::arg("h0"), py::arg("h1"), py::arg("h2"), py::arg("stream"),
+     "first launch of the two-launch step with momentum (kind 1) or adam (kind 2): applies the "
+     "pending update to the parameters and the slot planes (apply=0: copy, slots untouched) and "
+     "runs the forward; mlp_lean_head finishes the step");
+  m.def("mlp_apply_opt", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                            uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int par,
+                            int kind, uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1,
+                            float h2, uintptr_t s) {
+    dtfx::mlp_apply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<float>(ws),
+        P<int>(ctr), P<float>(stats), ring, B, par,
+        dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1, h2}, S(s));
+  }, "the flush of mlp_lean_fwdapply_opt: the pending update alone, p_old -> p_new");
+  struct MlpRunOptPlan {
+    float *p0, *p1;
+    const float* x;
+    const int* labels;
+    int nbatches;
+    float* ws;
+    int* ctr;
+    float* stats;
+    int ring, B;
+    dtfx::MlpOpt opt;
+  };
+  py::class_<MlpRunOptPlan>(m, "MlpRunOptPlan")
+      .def(py::init([](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
+                       uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int kind,
+                       uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1, float h2) {
+        return MlpRunOptPlan{P<float>(p0), P<float>(p1), P<const float>(x), P<const int>(lab),
+                             nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B,
+                             dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1,
+                                          h2}};
+      }))
+      .def("run", [](const MlpRunOptPlan& p, int cur, int pending, float lr, int pos, int n,
+                     int flush, uintptr_t s) {
+        py::gil_scoped_release nogil;
+        dtfx::mlp_run_pipelined_opt_launch(p.p0, p.p1, cur, pending, lr, p.x, p.labels,
+                                           p.nbatches, pos, n, p.ws, p.ctr, p.stats, p.ring, p.B,
+                                           S(s), flush, p.opt);
+      }, "(cur, pending, lr, pos, n, flush, stream): the C++ host loop of the two-launch step "
+         "with momentum / adam over the bound buffers (MlpRunPlan's call)");
   m.def("mlp_persistent_ll_words", &dtfx::mlp_persistent_ll_words);
   m.def("mlp_persistent_blocks", &dtfx::mlp_persistent_blocks);
   m.def("mlp_persistent_trace_steps", &dtfx::mlp_persistent_trace_steps);

@@ -48,6 +48,9 @@
 //   those slab stores written through (sc1): the boundary to the head shrinks by what the
 //     stores' own drain adds to the launch's tail, no gain per step;
 //   p_new written through as well: slower in the driver-sized run.
+// Momentum and Adam live in that first launch too (mlp_lean_fwdapply_opt_kernel, OptArgs below):
+// the lane that owns a parameter element also owns its slot values, so no gradient buffer and no
+// optimizer launch exist; the SGD instantiations are unchanged (profiles/fused_optim/).
 //
 // All MFMA work is v_mfma_f32_16x16x4_f32 (exact f32).  Lane l supplies
 // A[i = l&15][k = l>>4], B[k = l>>4][j = l&15]; C[row = (l>>4)*4 + r][col = l&15].
@@ -766,6 +769,65 @@ __device__ __forceinline__ void xg_exchange2(const MlpXg& xg, unsigned ep, const
   if (!fail) xgll::finish_wait_n<N>(result(me), off, other, ep, w2, v, xg.ticks, fail);
 }
 
+// ---------------------------------------------------------------------------
+// Stateful optimizers inside the lean two-launch step (mlp_lean_fwdapply_opt_kernel): gpu_ps.hip's
+// formulas (ops/optim.py's momentum_ / adam_, no weight decay, no Nesterov) applied by the lane
+// that owns the element -- the A16 item of fwdapply_block for W1, the ok[i] lane of wgrad_small
+// for b1 / W2 / b2.  The slot planes s0 (momentum: accum; adam: m) and s1 (adam: v) are flat f32
+// [NPARAM] buffers in the parameter layout, updated IN PLACE (one owner per element, read once
+// and written once by it); only the parameters ping-pong.
+//   momentum  accum = mu * accum + g;  p -= lr * accum   (mu = 0: accum = g and the SGD bits)
+//   adam      m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * g * g
+//             p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// t = global_step + 1 of the step being applied.  It is NOT read from ctr: the stats lane of the
+// small-parameter block jt == 0 writes ctr in this same launch.  tp is a pair of step words
+// indexed by the launch's buffer parity par (the index of p_old in the trainer's ping-pong pair):
+// every wave reads tp[par], the stats lane alone writes tp[par ^ 1] = tp[par] + stats_on, which
+// the NEXT launch (parity par ^ 1) reads -- no word is read and written in one launch.
+// apply == 0 (nothing pending): p_old is copied, no slot byte is written.
+enum : int { OPT_SGD = 0, OPT_MOMENTUM = 1, OPT_ADAM = 2 };
+struct OptArgs {
+  float* s0;
+  float* s1;
+  int* tp;
+  float h0, h1, h2;  // momentum: mu; adam: beta1, beta2, epsilon
+  int apply, par;
+};
+// momentum: lr, h0 = mu.  adam: lr = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t)
+struct OptCoef {
+  float lr, h0, h1, h2, rbc2;
+};
+template <int OPT>
+__device__ __forceinline__ OptCoef opt_coef(float lr, const OptArgs& oa) {
+  OptCoef c = {lr, oa.h0, oa.h1, oa.h2, 1.f};
+  if constexpr (OPT == OPT_ADAM) {  // (wave-uniform: once per wave, not per element)
+    // b^t = exp2(t log2 b) on the transcendental unit: 0 <= b < 1, so the product is <= 0, and
+    // wherever b^t is not negligible against 1 (t |log2 b| < 24) its relative error stays below
+    // 24 ulp of the exponent ~ 3e-6 -- 1e-6 of an update of ~lr.  powf would add ~6 KB of code
+    // per instantiation in front of the apply.
+    const float tf = (float)(oa.tp[oa.par] + 1);
+    c.lr = lr / (1.f - __builtin_amdgcn_exp2f(tf * __builtin_amdgcn_logf(oa.h0)));
+    c.rbc2 = rsqrtf(1.f - __builtin_amdgcn_exp2f(tf * __builtin_amdgcn_logf(oa.h1)));
+  }
+  return c;
+}
+// -> the new parameter value; s0 / s1 become the new slot values
+template <int OPT>
+__device__ __forceinline__ float opt_update(float p, float g, float& s0, float& s1,
+                                            const OptCoef& c) {
+  if constexpr (OPT == OPT_MOMENTUM) {
+    s0 = c.h0 * s0 + g;
+    return p - c.lr * s0;
+  } else {
+    s0 = c.h0 * s0 + (1.f - c.h0) * g;
+    s1 = c.h1 * s1 + (1.f - c.h1) * g * g;
+    // v_sqrt_f32 / v_rcp_f32 (1 ulp each) instead of the correctly rounded sqrtf and division
+    // (~25 instructions per element between the LDS sum and the Wt / p_new stores): 2 ulp of an
+    // update of ~lr, far below half an ulp of p
+    return p - c.lr * s0 * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(s1) * c.rbc2 + c.h2);
+  }
+}
+
 // Small parameters of hidden tile jt (one product per wave), shared by mlp_wgrad_kernel and
 // mlp_wgrad_factor_kernel; eidx = this wave's exchange-epoch slot.
 // p_src: where the current parameter values are read (== p except in the pipelined step,
@@ -773,14 +835,18 @@ __device__ __forceinline__ void xg_exchange2(const MlpXg& xg, unsigned ep, const
 // loss/accuracy record and the global_step increment.
 // RM: the factors are read from the row-major regions dz1R / dlR (one value per lane and batch
 // row; the same (group, element) -> row order of the K sum as the transposed form's float4).
-template <bool DIRECT, int NGT, int XW, bool RM = false>
+// OPT (the lean step's optimizer variants; DIRECT, no exchange): the owning lane also reads and
+// rewrites its slot values (addresses clamped like p_src's, stores behind the p store's
+// predicate and oa.apply); the stats lane hands the step word on (tp[par ^ 1]).
+template <bool DIRECT, int NGT, int XW, bool RM = false, int OPT = OPT_SGD>
 __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx,
                                             float* __restrict__ p, float lr,
                                             float* __restrict__ grad, const Bufs& w,
                                             int* __restrict__ ctr, float* __restrict__ stats,
                                             int stats_ring, int B, const MlpXg& xg,
                                             const float* __restrict__ p_src = nullptr,
-                                            int stats_on = 1) {
+                                            int stats_on = 1, const OptArgs& oa = OptArgs{}) {
+  static_assert(OPT == OPT_SGD || (DIRECT && XW == 0), "optimizer variants: the lean step only");
   if (p_src == nullptr) p_src = p;
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
   const int NG = NGT > 0 ? NGT : BP / 16;
@@ -797,6 +863,9 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   int role = wave;  // 0 / 2 (SPLIT): dW2 (halves), 1: db1, 2 (!SPLIT): db2, 3: stats (+ db2)
   if (wave == 3) {
     if (jt != 0) return;
+    if constexpr (OPT != OPT_SGD) {  // the next launch's step word (this one reads tp[par])
+      if (lane == 0) oa.tp[oa.par ^ 1] = oa.tp[oa.par] + (stats_on ? 1 : 0);
+    }
     if (stats_on) {
       float l = 0.f, a = 0.f;
       for (int b = lane; b < B; b += 64) {
@@ -858,6 +927,7 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   size_t off[4];
   bool ok[4];
   float pv[4];
+  float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};  // OPT: slot values
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     if (dw2) {  // C[c = q*4+i][j = jt*16 + r] -> dW2t[c][j]; SPLIT: wave 0 i < 2, wave 2 i >= 2
@@ -874,9 +944,13 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
       off[i] = OFF_B2 + (c < C ? c : 0);
     }
     if (DIRECT) pv[i] = p_src[off[i]];
+    if constexpr (OPT != OPT_SGD) sa[i] = oa.s0[off[i]];
+    if constexpr (OPT == OPT_ADAM) sb[i] = oa.s1[off[i]];
   }
   (void)db2;
   __builtin_amdgcn_sched_barrier(0);
+  [[maybe_unused]] OptCoef oc = {};  // (adam's b1^t / b2^t while the loads are in flight)
+  if constexpr (OPT != OPT_SGD) oc = opt_coef<OPT>(lr, oa);
   // NB: padded batch columns of dz1T/dlT are zero, so multiplying by 1 is exact.
   f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
 #pragma unroll
@@ -929,6 +1003,21 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
     } else {
       xg_exchange<XW>(xg, ep, off, ok, v, fail);
     }
+  }
+  if constexpr (OPT != OPT_SGD) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // (computed by every lane and selected: oa.apply == 0 copies p and leaves the slots)
+      const float pn = opt_update<OPT>(pv[i], v[i], sa[i], sb[i], oc);
+      if (ok[i]) {
+        p[off[i]] = oa.apply ? pn : pv[i];
+        if (oa.apply) {
+          oa.s0[off[i]] = sa[i];
+          if constexpr (OPT == OPT_ADAM) oa.s1[off[i]] = sb[i];
+        }
+      }
+    }
+    return;
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -1085,16 +1174,23 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(
 // first MFMA's vmcnt leaves pw and xa in flight, the apply waits for pw alone), the four
 // partials read back from LDS as one float4 per wave and added in wave order, one float4 store
 // each to p_new and Wt -- instead of waves 0 / 1 moving four dwords at stride D each.
+// OPT (momentum / adam, on top of A16; see OptArgs): the item's slot float4s are requested at
+// the pw position, right after pw4 (same clamped address in the slot planes), so the first
+// MFMA's vmcnt still waits for phase A's operands only and the apply waits for pw4 and the
+// slots; the new slot values go back through the p_new store's predicate.  The update is
+// computed by every lane and selected by oa.apply (no branch around the loads' uses, which
+// would let the compiler sink them below the barrier).
 template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true,
-          bool ORD = false, bool A16 = false>
+          bool ORD = false, bool A16 = false, int OPT = OPT_SGD>
 __device__ __forceinline__ void fwdapply_block(
     const int bid, const float* __restrict__ p_old, float* __restrict__ p_new, float lr,
     const float* __restrict__ x_prev, const float* __restrict__ x, const Bufs& w,
     int* __restrict__ ctr, float* __restrict__ stats, int stats_ring, int B, int stats_on,
     const MlpXg& xg, unsigned long long* __restrict__ tr,
-    unsigned long long* __restrict__ trs = nullptr) {
+    unsigned long long* __restrict__ trs = nullptr, const OptArgs& oa = OptArgs{}) {
   static_assert(!ORD || (XW == 0 && KSX == KS3), "load order of the row-quad form");
   static_assert(!A16 || ORD, "the 16-byte apply belongs to the lean step");
+  static_assert(OPT == OPT_SGD || (A16 && !TRACE), "optimizer variants: the lean step only");
   // stamps per wave: 0 entry, 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab
   // stored; with XW > 0 also 4 local gradient slice ready (exchange starts), 5 two-shot: the
   // owned sums done (first hop), 6 exchange done -- 8 slots per wave then
@@ -1116,6 +1212,10 @@ __device__ __forceinline__ void fwdapply_block(
   constexpr bool RM = XW == 0 && KSX == KS3;
   if (bid >= HT * KSX) {
     const int jt = bid - HT * KSX;
+    if constexpr (OPT != OPT_SGD)
+      wgrad_small<true, NGT, XW, RM, OPT>(jt, wave, lane, 0, p_new, lr, nullptr, w, ctr, stats,
+                                          stats_ring, B, xg, p_old, stats_on, oa);
+    else
     wgrad_small<true, NGT, XW, RM>(jt, wave, lane, MLP_XG_SMALL_EPOCH + jt * 4 + wave, p_new, lr,
                                nullptr, w, ctr, stats, stats_ring, B, xg, p_old, stats_on);
     if (TRACE) trace_stamp(trw, 3);
@@ -1170,9 +1270,14 @@ __device__ __forceinline__ void fwdapply_block(
     const int item = wave * IPW + (lane < IPW ? lane : IPW - 1);
     const int hw = item / MQ, mw = item % MQ, jw = jt * 16 + hw;
     float4 pw4 = {0.f, 0.f, 0.f, 0.f};
+    float4 sa4 = {0.f, 0.f, 0.f, 0.f}, sb4 = {0.f, 0.f, 0.f, 0.f};  // OPT: the item's slot values
     auto load_pw = [&]() {
       if constexpr (A16) {
         pw4 = f4(p_old + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
+        if constexpr (OPT != OPT_SGD)
+          sa4 = f4(oa.s0 + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
+        if constexpr (OPT == OPT_ADAM)
+          sb4 = f4(oa.s1 + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
       } else if (wave < 2) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -1201,6 +1306,9 @@ __device__ __forceinline__ void fwdapply_block(
       load_xa();
     }
     __builtin_amdgcn_sched_barrier(0);  // all loads in flight together
+    // (OPT: adam's b1^t / b2^t while the loads are in flight, not between the sum and the store)
+    [[maybe_unused]] OptCoef oc = {};
+    if constexpr (OPT != OPT_SGD) oc = opt_coef<OPT>(lr, oa);
     if constexpr (TRACE && NGT > 0 && FWD) {
       if (trs) {  // loads issued after the first class: ORD pw + xa, else pw + the factors
         unsigned long long* t2 = trs + (size_t)(bid * 4 + wave) * 2;
@@ -1234,8 +1342,22 @@ __device__ __forceinline__ void fwdapply_block(
       }
       const bool live = jw < H;
       float4 v;
+      if constexpr (OPT != OPT_SGD) {
+        v.x = opt_update<OPT>(pw4.x, part.x, sa4.x, sb4.x, oc);
+        v.y = opt_update<OPT>(pw4.y, part.y, sa4.y, sb4.y, oc);
+        v.z = opt_update<OPT>(pw4.z, part.z, sa4.z, sb4.z, oc);
+        v.w = opt_update<OPT>(pw4.w, part.w, sa4.w, sb4.w, oc);
+        if (!oa.apply) v = pw4;  // nothing pending: a copy, and no slot byte is written
+        if (oa.apply && lane < IPW && live) {
+          float* so = oa.s0 + OFF_W1 + (size_t)jw * D + f0 + 4 * mw;
+          *reinterpret_cast<float4*>(so) = sa4;
+          if constexpr (OPT == OPT_ADAM)
+            *reinterpret_cast<float4*>(oa.s1 + (so - oa.s0)) = sb4;
+        }
+      } else {
       v.x = pw4.x - lr * part.x, v.y = pw4.y - lr * part.y;
       v.z = pw4.z - lr * part.z, v.w = pw4.w - lr * part.w;
+      }
       // (every lane: the LDS store also keeps the pw load above the barrier, where it was issued)
       if (FWD)  // padded hidden rows contribute exact zeros
         *reinterpret_cast<float4*>(&Wt[hw][4 * mw]) = live ? v : float4{0.f, 0.f, 0.f, 0.f};
@@ -1484,14 +1606,19 @@ __global__ __launch_bounds__(256) void mlp_fwdapply_kernel(
 // The data-parallel engines, mlp_fwdapply_launch / mlp_head2_launch and the opt-in fused flush
 // keep mlp_fwdapply_kernel / mlp_head_kernel.
 
-template <int NGT, bool TRACE, bool FWD>
+template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD>
 __device__ __forceinline__ void lean_fwdapply_body(
     const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
     const float* __restrict__ x, float* __restrict__ ws, int* __restrict__ ctr,
     float* __restrict__ stats, float lr, int flags, unsigned long long* __restrict__ tr,
-    unsigned long long* __restrict__ trs) {
+    unsigned long long* __restrict__ trs, const OptArgs& oa = OptArgs{}) {
   const int B = flags & 511, stats_on = (flags >> 9) & 1, stats_ring = flags >> 10;
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
+  if constexpr (OPT != OPT_SGD)
+    fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT>(
+        blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{},
+        tr, trs, oa);
+  else
   fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true>(
       blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{}, tr,
       trs);
@@ -1504,6 +1631,21 @@ __global__ __launch_bounds__(256) void mlp_lean_fwdapply_kernel(
     int* __restrict__ ctr, float* __restrict__ stats) {
   lean_fwdapply_body<NGT, false, FWD>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags, nullptr,
                                       nullptr);
+}
+
+// The momentum / adam instantiations (OptArgs): the SGD kernel's nine arguments, then the slot
+// planes, the step pair, the three hyper-parameter words (gpu_ps_optim.hyper_args) and
+// oflags = apply | par << 1.
+template <int NGT, bool FWD, int OPT>
+__global__ __launch_bounds__(256) void mlp_lean_fwdapply_opt_kernel(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, float lr, int flags,
+    int* __restrict__ ctr, float* __restrict__ stats, float* __restrict__ s0,
+    float* __restrict__ s1, int* __restrict__ tp, float h0, float h1, float h2, int oflags) {
+  static_assert(OPT == OPT_MOMENTUM || OPT == OPT_ADAM, "stateful kinds");
+  const OptArgs oa = {s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1};
+  lean_fwdapply_body<NGT, false, FWD, OPT>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags,
+                                           nullptr, nullptr, oa);
 }
 
 template <int NGT>
@@ -2605,6 +2747,125 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
     const int prev = (pos + nbatches - 1) % nbatches;
     mlp_apply_launch(bufs[cur], bufs[cur ^ 1], lr, x + (size_t)prev * xb, ws, ctr, stats,
                      stats_ring, B, stream);
+  }
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Momentum / Adam inside the two-launch step (mlp_lean_fwdapply_opt_kernel; the head launch is
+// the SGD step's).  kind: 1 momentum, 2 adam; s0 / s1: the slot planes (flat f32 [79510],
+// 16-byte aligned; s1 adam only); tp: the int32[2] step pair; h0..h2: gpu_ps_optim.hyper_args.
+// par is the index of p_old in the caller's ping-pong pair: the launch reads tp[par] and writes
+// tp[par ^ 1], so consecutive launches must alternate it (as they alternate the buffers).
+// Only the lean 28-slice step has these variants: DTFX_MLP_KS=14 and the fused flush
+// (DTFX_MLP_FLUSH_FUSED) are refused.
+struct MlpOpt {
+  int kind;
+  float *s0, *s1;
+  int* tp;
+  float h0, h1, h2;
+};
+
+static void check_opt(const MlpOpt& o, const char* who) {
+  const std::string w(who);
+  if (o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
+    throw std::runtime_error(w + ": optimizer kind must be 1 (momentum) or 2 (adam)");
+  if (mlp_single_ks() != mlp::KS3)
+    throw std::runtime_error(w + ": DTFX_MLP_KS=14 has no optimizer variant (sgd only)");
+  if (!o.s0 || !o.tp || (o.kind == mlp::OPT_ADAM && !o.s1))
+    throw std::runtime_error(w + ": null slot plane / step pair");
+  if ((reinterpret_cast<uintptr_t>(o.s0) | reinterpret_cast<uintptr_t>(o.s1)) & 15)
+    throw std::runtime_error(w + ": slot planes must be 16-byte aligned");
+}
+
+template <bool FWD>
+static void lean_first_opt_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
+                                  const float* x, float* ws, int* ctr, float* stats,
+                                  int stats_ring, int B, int apply, int par, const MlpOpt& o,
+                                  hipStream_t stream) {
+  using namespace mlp;
+  const int flags = lean_flags(B, apply, stats, stats_ring);
+  if ((reinterpret_cast<uintptr_t>(p_old) | reinterpret_cast<uintptr_t>(p_new)) & 15)
+    throw std::runtime_error("fused MLP step: parameter buffers must be 16-byte aligned");
+  const int oflags = (apply ? 1 : 0) | (par & 1) << 1;
+  dim3 grid(HT * KS3 + HT), block(256);
+#define DTFX_LO(NGT, OPTK)                                                                       \
+  hipLaunchKernelGGL((mlp_lean_fwdapply_opt_kernel<NGT, FWD, OPTK>), grid, block, 0, stream,     \
+                     p_old, p_new, x_prev, x, ws, lr, flags, ctr, stats, o.s0, o.s1, o.tp, o.h0, \
+                     o.h1, o.h2, oflags)
+  const bool rt7 = (B + 15) / 16 == 7;
+  if (o.kind == OPT_MOMENTUM) {
+    if (rt7) DTFX_LO(7, OPT_MOMENTUM);
+    else DTFX_LO(0, OPT_MOMENTUM);
+  } else {
+    if (rt7) DTFX_LO(7, OPT_ADAM);
+    else DTFX_LO(0, OPT_ADAM);
+  }
+#undef DTFX_LO
+}
+
+// First launch of a step: apply != 0 applies the pending update (and records its stats, global
+// step += 1); apply == 0 copies p_old -> p_new, touches no slot byte and runs the forward.
+void mlp_lean_fwdapply_opt_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
+                                  const float* x, float* ws, int* ctr, float* stats,
+                                  int stats_ring, int B, int apply, int par, const MlpOpt& o,
+                                  hipStream_t stream) {
+  check_b(B);
+  check_opt(o, "mlp_lean_fwdapply_opt");
+  if (!p_old || !p_new || p_old == p_new || !x_prev || !x || !ctr || !ws)
+    throw std::runtime_error(
+        "mlp_lean_fwdapply_opt: needs distinct ping-pong buffers, both batches, ctr");
+  lean_first_opt_launch<true>(p_old, p_new, lr, x_prev, x, ws, ctr, stats, stats_ring, B, apply,
+                              par, o, stream);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// The flush: the pending update alone (apply-only instantiation), p_old -> p_new.
+void mlp_apply_opt_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
+                          float* ws, int* ctr, float* stats, int stats_ring, int B, int par,
+                          const MlpOpt& o, hipStream_t stream) {
+  check_b(B);
+  check_opt(o, "mlp_apply_opt");
+  if (!p_old || !p_new || p_old == p_new || !x_prev || !ctr || !ws)
+    throw std::runtime_error("mlp_apply_opt: needs distinct ping-pong buffers, the batch, ctr");
+  lean_first_opt_launch<false>(p_old, p_new, lr, x_prev, x_prev, ws, ctr, stats, stats_ring, B, 1,
+                               par, o, stream);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// mlp_run_pipelined_launch with an optimizer: the same walk over the resident dataset, buffer
+// parity and flush; every first launch takes par = the parity it reads.
+void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, float lr,
+                                  const float* x, const int* labels, int nbatches, int pos, int n,
+                                  float* ws, int* ctr, float* stats, int stats_ring, int B,
+                                  hipStream_t stream, int flush, const MlpOpt& o) {
+  using namespace mlp;
+  check_b(B);
+  check_opt(o, "mlp_run_pipelined_opt");
+  if (!p0 || !p1 || p0 == p1 || !x || !labels || !ctr || !ws || nbatches < 1 || pos < 0 ||
+      pos >= nbatches || n < 0 || (cur != 0 && cur != 1))
+    throw std::runtime_error("mlp_run_pipelined_opt: bad buffers / position / count");
+  if (flush && mlp_flush_fused())
+    throw std::runtime_error("mlp_run_pipelined_opt: the fused flush (DTFX_MLP_FLUSH_FUSED) has "
+                             "no optimizer variant (sgd only)");
+  float* bufs[2] = {p0, p1};
+  const size_t xb = (size_t)B * D;
+  for (int i = 0; i < n; ++i) {
+    const int prev = (pos + nbatches - 1) % nbatches;
+    const float* xcur = x + (size_t)pos * xb;
+    const float* xprev = pending ? x + (size_t)prev * xb : xcur;
+    lean_first_opt_launch<true>(bufs[cur], bufs[cur ^ 1], lr, xprev, xcur, ws, ctr, stats,
+                                stats_ring, B, pending, cur, o, stream);
+    lean_head_launch(bufs[cur ^ 1], labels + (size_t)pos * B, ws, B, stream);
+    cur ^= 1;
+    pending = 1;
+    pos = (pos + 1) % nbatches;
+  }
+  if (flush && pending) {
+    const int prev = (pos + nbatches - 1) % nbatches;
+    lean_first_opt_launch<false>(bufs[cur], bufs[cur ^ 1], lr, x + (size_t)prev * xb,
+                                 x + (size_t)prev * xb, ws, ctr, stats, stats_ring, B, 1, cur, o,
+                                 stream);
   }
   DTFX_HIP_CHECK(hipGetLastError());
 }

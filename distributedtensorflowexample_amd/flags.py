@@ -202,11 +202,14 @@ def define_reference_flags(flag_values=FLAGS):
                   "worker (pull / apply / global_step over xGMI; with --sync_replicas the "
                   "rounds run on the device too: gradient slots, one apply of the mean)", fv)
     DEFINE_string("optimizer", "sgd",
-                  "ps_async strategy: sgd (GradientDescentOptimizer, the reference) | momentum | "
-                  "adam (tf.train.MomentumOptimizer / AdamOptimizer).  momentum and adam need "
+                  "sgd (GradientDescentOptimizer, the reference) | momentum | adam "
+                  "(tf.train.MomentumOptimizer / AdamOptimizer).  ps_async: momentum and adam need "
                   "--ps_device gpu: their slot variables live in the GPU store next to the "
                   "variables, the store's kernels update them (async and --sync_replicas) and "
-                  "checkpoints carry them; not with --use_locking", fv)
+                  "checkpoints carry them; not with --use_locking.  mirrored, --model mlp: "
+                  "applied inside the fused two-launch step (one GPU), by the all-reduce engine "
+                  "(several) or the autograd path (--device cpu); slots in the checkpoints; "
+                  "not with --zero1", fv)
     DEFINE_float("momentum", 0.9, "--optimizer momentum: the momentum", fv)
     DEFINE_float("adam_beta1", 0.9, "--optimizer adam: beta1", fv)
     DEFINE_float("adam_beta2", 0.999, "--optimizer adam: beta2", fv)

@@ -172,6 +172,68 @@ def flush_pipelined(p_old, p_new, x_prev, ws: StepWorkspace, lr, stats=True):
                     ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, stream_handle())
 
 
+class PipelinedOpt:
+    """Momentum / Adam state of the two-launch step (``csrc/kernels/mlp_step.hip``, OptArgs):
+    ``slots`` -- one (momentum: accum) or two (adam: m, v) flat f32 [79510] planes in the
+    parameter layout, updated in place by the lane that owns each element; ``tp`` -- the int32
+    [2] step pair (a launch of buffer parity ``par`` reads ``tp[par]`` = global_step of the step
+    it applies, Adam's ``t - 1``, and writes ``tp[par ^ 1]``); ``hyper`` --
+    ``gpu_ps_optim.hyper_args``' three words."""
+
+    KINDS = {"momentum": 1, "adam": 2}
+
+    def __init__(self, kind, device, momentum=0.9, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        from ..parallel import gpu_ps_optim
+
+        if kind not in self.KINDS:
+            raise ValueError("the fused step's optimizers are momentum and adam, got %r" % (kind,))
+        self.kind = kind
+        self.code = self.KINDS[kind]
+        self.hyper = gpu_ps_optim.hyper_args(kind, momentum, beta1, beta2, epsilon)
+        self.slots = [torch.zeros(NPARAM, device=device, dtype=torch.float32)
+                      for _ in range(gpu_ps_optim.num_slots(kind))]
+        self.tp = torch.zeros(2, device=device, dtype=torch.int32)
+        _check_flat(*self.slots)
+
+    def set_step(self, s):
+        """Both words: the next launch reads the right one whatever its parity."""
+        self.tp.fill_(int(s))
+
+    def args(self):
+        """(kind, s0, s1, tp, h0, h1, h2) as the launchers take them."""
+        s = self.slots
+        return (self.code, ptr(s[0]), ptr(s[1]) if len(s) > 1 else 0, ptr(self.tp)) + self.hyper
+
+
+def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, par,
+                       opt: PipelinedOpt, stats=True):
+    """``step_pipelined`` with momentum / Adam: the first launch applies the pending update to
+    ``p_old -> p_new`` AND, in place, to ``opt.slots`` (Adam's ``t`` = ``opt.tp[par] + 1``).
+    ``apply=False`` is an explicit bit here: a copy + forward that leaves every slot byte alone.
+    ``par``: the index of ``p_old`` in the caller's ping-pong pair; consecutive launches
+    alternate it.  The head launch is ``step_pipelined``'s."""
+    _check(x, labels, ws.B)
+    _check(x_prev, None, ws.B)
+    _check_flat(p_old, p_new)
+    if p_old.data_ptr() == p_new.data_ptr():
+        raise ValueError("the pipelined step needs distinct ping-pong buffers")
+    h, s = hip(), stream_handle()
+    h.mlp_lean_fwdapply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x), ptr(x),
+                            ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
+                            ws.stats_ring, ws.B, 1 if apply else 0, int(par), *opt.args(), s)
+    h.mlp_lean_head(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s)
+
+
+def flush_pipelined_opt(p_old, p_new, x_prev, ws: StepWorkspace, lr, par, opt: PipelinedOpt,
+                        stats=True):
+    """``flush_pipelined`` with momentum / Adam (the apply-only instantiation)."""
+    _check(x_prev, None, ws.B)
+    _check_flat(p_old, p_new)
+    hip().mlp_apply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev), ptr(ws.buf), ptr(ws.ctr),
+                        ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, int(par),
+                        *opt.args(), stream_handle())
+
+
 def step_xgmi(p, x, labels, ws: StepWorkspace, lr, comm, stats=True):
     """One synchronous data-parallel SGD step in place on ``p`` with the gradient exchange
     fused into the weight-gradient kernel (``comm``: an ``XgmiComm`` with protocol "push";

@@ -45,7 +45,23 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   differs every epoch.  The update pending across a boundary reads the previous
   epoch's last batch from the OTHER buffer -- hence two; the C++ host loops,
   which wrap inside one base pointer, are called once per epoch, and the
-  persistent launch, which wraps inside the kernel, is refused.
+  persistent launch, which wraps inside the kernel, is refused;
+* ``optimizer="momentum" | "adam"`` (``--optimizer``): the trainer owns zero-initialised
+  slot planes (``slots``: momentum ``[accum]``, adam ``[m, v]``; flat f32 [79510] in the
+  parameter layout) and ``parallel/gpu_ps_optim.py``'s formulas are applied INSIDE the
+  two-launch step: ``mlp_lean_fwdapply_opt`` forms each W1 tile's gradient in registers as the
+  SGD step does, and the lane that owns an element reads and rewrites its slot values next to
+  the parameter (slots in place, parameters ping-pong; no gradient buffer, no third launch).
+  "Nothing to apply" is an explicit bit (a copy that leaves the slots alone), and Adam's ``t``
+  is ``global_step + 1`` of the step being applied, read from a two-word step pair indexed by
+  the buffer parity (``ops.mlp_step.PipelinedOpt``) -- never from the counter the same launch
+  advances.  ``seek`` sets it, so a restored ``global_step`` restores ``t``.  Graph replay,
+  ``run_launched`` (``MlpRunOptPlan``), ``flush``, ``snapshot``, ``evaluate`` and the stats
+  work as with sgd; the persistent launch, the three-launch direct step, ``DTFX_MLP_KS=14``,
+  the fused flush and the exchange engines are sgd-only and refuse an optimizer.  Data
+  parallel: the all-reduce engine applies the reduced gradient with ``ops.optim``'s
+  ``scale_`` + ``momentum_`` / ``adam_`` in place (``t`` from the device counter) before the
+  next step's launches.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -61,13 +77,25 @@ import torch
 
 from ..ops import mlp_step, optim
 from ..ops._ext import stream_handle
+from ..parallel import gpu_ps_optim
 
 
 class FusedMLPTrainer:
     def __init__(self, params, x, labels, batch_size=100, learning_rate=0.001, allreduce=None,
                  world_size=1, stats_ring=4096, global_step=0, max_graph_steps=1024,
                  fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
-                 shuffle=False, shuffle_seed=0):
+                 shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
+                 beta2=0.999, epsilon=1e-8):
+        # --optimizer momentum | adam: refused first where only gradient descent exists
+        self.optimizer = gpu_ps_optim.check_kind(optimizer)
+        if self.optimizer != "sgd":
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("optimizer %s: the exchange engines (fused_comm / factor_comm) "
+                                 "apply gradient descent only; use the all-reduce engine"
+                                 % self.optimizer)
+            if not pipeline and allreduce is None and int(world_size) == 1:
+                raise ValueError("optimizer %s: the three-launch direct step (pipeline=False) "
+                                 "applies gradient descent only" % self.optimizer)
         if not params.is_cuda:
             raise ValueError("FusedMLPTrainer runs on the GPU; use the generic path on CPU")
         if params.numel() != mlp_step.NPARAM:
@@ -117,6 +145,12 @@ class FusedMLPTrainer:
             (self.world_size == 1 and factor_comm is None and fused_comm is None)
             or fused_comm is not None
             or (factor_comm is not None and self.B <= 128)))
+        # --optimizer momentum | adam (module docstring): slot planes owned by the trainer
+        self.opt = None
+        if self.optimizer != "sgd":
+            self.opt = mlp_step.PipelinedOpt(self.optimizer, self.device, momentum, beta1, beta2,
+                                             epsilon)
+            self.opt.set_step(global_step)
         self.max_graph_steps = int(max_graph_steps)
         self._graphs = {}
         self._pool = None
@@ -161,6 +195,43 @@ class FusedMLPTrainer:
         self._verified()
         return self.bufs[self.cur]
 
+    @property
+    def slots(self):
+        """The optimizer's slot planes (momentum: [accum]; adam: [m, v]; sgd: []), flat f32
+        [79510] in the parameter layout -- like ``params``, without a pending update."""
+        self._verified()
+        return [] if self.opt is None else self.opt.slots
+
+    def load_slots(self, slots):
+        """Set the slot planes (a restored checkpoint's); as ``load_params``, nothing is
+        pending afterwards."""
+        own = self.slots
+        slots = list(slots)
+        if len(slots) != len(own):
+            raise ValueError("optimizer %s has %d slot planes, got %d"
+                             % (self.optimizer, len(own), len(slots)))
+        for d, t in zip(own, slots):
+            d.copy_(t.reshape(-1))
+        self.pending = False
+
+    @property
+    def _inplace(self):
+        """All-reduce engine with an optimizer: the reduced gradient is applied in place on the
+        current buffer (``ops.optim``), so the parity never moves."""
+        return self.opt is not None and not self.pipelined
+
+    def _apply_reduced(self, p, slots):
+        """The pending all-reduced gradient through the optimizer, in place on ``p`` /
+        ``slots`` (graph-capturable: Adam's t is the device counter, which the step that
+        produced the gradient already advanced to its ``global_step + 1``)."""
+        optim.scale_(self.grad, 1.0 / self.world_size)
+        h = self.opt.hyper
+        if self.optimizer == "momentum":
+            optim.momentum_(p, self.grad, slots[0], self.lr, momentum=h[0])
+        else:
+            optim.adam_(p, self.grad, slots[0], slots[1], self.lr, 0, beta1=h[0], beta2=h[1],
+                        eps=h[2], weight_decay=0.0, adamw=False, step_tensor=self.ws.ctr)
+
     def flush(self):
         """Apply the pending update in place (DP: p -= lr/N * grad; pipelined: the last
         step's factors)."""
@@ -175,27 +246,49 @@ class FusedMLPTrainer:
                 mlp_step.flush_xgmi(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, self.ws,
                                     self.lr / self.world_size, self.fused_comm)
                 self.cur ^= 1
+            elif self.pipelined and self.opt is not None:
+                xp = self._xprev(self.pos)
+                mlp_step.flush_pipelined_opt(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp,
+                                             self.ws, self.lr, self.cur, self.opt)
+                self.cur ^= 1
             elif self.pipelined:
                 xp = self._xprev(self.pos)
                 mlp_step.flush_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, self.ws,
                                          self.lr)
                 self.cur ^= 1
+            elif self.opt is not None:
+                self._apply_reduced(self.bufs[self.cur], self.opt.slots)
             else:
                 optim.sgd_(self.bufs[self.cur], self.grad, self.lr / self.world_size)
             self.pending = False
         return self.bufs[self.cur]
 
-    def snapshot(self):
-        """Parameters after every step run so far (a pending update included) as a NEW
+    def snapshot(self, with_slots=False):
+        """``with_slots``: ``(parameters, [slot planes])`` instead, the slots by the same rules
+        (new tensors; an optimizer's pending all-reduced gradient is applied to copies of the
+        parameters AND the slots, so the trainer's state does not move).
+
+        Parameters after every step run so far (a pending update included) as a NEW
         tensor, WITHOUT changing the trainer: no peer exchange starts and the replicas' update
         sequence is untouched, so one rank alone may call it (chief-only checkpoints and
         evals).  The all-reduce engine's pending gradient is already reduced: applied to a
         copy.  A pending update of the pipelined exchange engines needs every rank's
         exchange: raises (call flush() on every rank instead)."""
         self._verified()
+        if with_slots:
+            if self.pending and self._inplace:
+                out, sl = self.bufs[self.cur].clone(), [t.clone() for t in self.opt.slots]
+                g = self.grad.clone()  # (_apply_reduced scales the gradient in place)
+                self._apply_reduced(out, sl)
+                self.grad.copy_(g)
+                return out, sl
+            out = self.snapshot()  # (pipelined on one GPU: flushed; slots then current)
+            return out, [t.clone() for t in self.slots]
         p = self.bufs[self.cur]
         if not self.pending:
             return p.clone()
+        if self._inplace:
+            return self.snapshot(with_slots=True)[0]
         if not self.pipelined:
             out = p.clone()
             optim.sgd_(out, self.grad, self.lr / self.world_size)
@@ -272,6 +365,8 @@ class FusedMLPTrainer:
         self.flush()
         s = int(global_step)
         self.ws.set_global_step(s)
+        if self.opt is not None:
+            self.opt.set_step(s)  # Adam's t of the next applied step: s + 1
         self.pos = s % self.nbatches
         if self.shuffle:
             self._bind(s // self.nbatches)
@@ -309,6 +404,13 @@ class FusedMLPTrainer:
         if self.direct:
             mlp_step.step_direct(self.bufs[self.cur], xb, yb, self.ws, self.lr)
             return
+        if self.pipelined and self.opt is not None:
+            xp = self._xprev(p0)
+            mlp_step.step_pipelined_opt(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
+                                        self.ws, self.lr, self.pending, self.cur, self.opt)
+            self.cur ^= 1
+            self.pending = True
+            return
         if self.pipelined:
             xp = self._xprev(p0)
             mlp_step.step_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
@@ -317,7 +419,13 @@ class FusedMLPTrainer:
             self.pending = True
             return
         cur = self.bufs[self.cur]
-        if self.pending:
+        if self.opt is not None:
+            # all-reduce engine with an optimizer: the reduced gradient of the previous step
+            # through ops.optim in place, then the step without its deferred apply
+            if self.pending:
+                self._apply_reduced(cur, self.opt.slots)
+            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad)
+        elif self.pending:
             mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, prev_grad=self.grad,
                                lr=self.lr / self.world_size, p_new=self.bufs[self.cur ^ 1])
             self.cur ^= 1
@@ -399,7 +507,13 @@ class FusedMLPTrainer:
             from ..ops._ext import hip, ptr
 
             ws = self.ws
-            if os.environ.get("DTFX_MLP_PLAN", "1") != "0":
+            if self.opt is not None:  # the optimizer form of the plan (slot pointers bound too)
+                plan = hip().MlpRunOptPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
+                                           ptr(self.labels), self.nbatches, ptr(ws.buf),
+                                           ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, self.B,
+                                           *self.opt.args())
+                a = self._host_args = (plan.run, self.device.index, None)
+            elif os.environ.get("DTFX_MLP_PLAN", "1") != "0":
                 # the buffers bound once in a C++ plan: the call before the first kernel
                 # converts 7 arguments instead of 17 (a short timed region starts on the host)
                 plan = hip().MlpRunPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
@@ -476,7 +590,7 @@ class FusedMLPTrainer:
         """The plain single-GPU step with batch <= 128 can run as ONE persistent launch (not in
         shuffle mode: that launch wraps around one dataset buffer inside the kernel)."""
         return (self.host_loop_ok and self.world_size == 1 and self.B <= 128
-                and not self.shuffle)
+                and not self.shuffle and self.opt is None)
 
     def run_persistent(self, steps, timeout_s=2.0, trace=None):
         """``steps`` complete SGD steps (every update applied, nothing left pending) in ONE
@@ -490,7 +604,7 @@ class FusedMLPTrainer:
         steps = int(steps)
         if not self.persistent_ok:
             raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
-                               "(and shuffle off)")
+                               "(shuffle off, optimizer sgd)")
         if steps <= 0:
             return
         self.flush()  # a pending pipelined update is applied first (params exact)
@@ -542,7 +656,7 @@ class FusedMLPTrainer:
         for n in self._plan(steps):
             self._graph(n).replay()
             self.pos = (self.pos + n) % self.nbatches
-            if not self.direct:
+            if not self.direct and not self._inplace:
                 self.cur ^= n & 1
             if self.shuffle and self.pos == 0:  # the next epoch's gather, between two replays
                 self._wrapped()
@@ -563,7 +677,7 @@ class FusedMLPTrainer:
         for n in self._plan(steps):
             self._graph(n)
             self.pos = (self.pos + n) % self.nbatches
-            if not self.direct:
+            if not self.direct and not self._inplace:
                 self.cur ^= n & 1
             if self.shuffle and self.pos == 0:
                 self._bind(self.epoch + 1)  # (host mirrors only: which buffer the graph reads)

@@ -22,6 +22,7 @@ import torch.distributed as dist
 from ..models import mlp as mlp_model
 from ..ops import mlp_step, nn, optim
 from ..ops.shuffle import shuffle_index
+from ..parallel import gpu_ps_optim
 from ..parallel.comm import NativeComm, TorchComm
 from ..parallel.watchdog import init_process_group_with_timeout, maybe_inject_fault, watch_peers
 from ..optim import GradientDescentOptimizer
@@ -31,7 +32,7 @@ from ..utils.summary import FileWriter
 from .fused_mlp import FusedMLPTrainer
 from .saver import FastSaver
 from .supervisor import Supervisor
-from .worker import flat_to_tf_vars, tf_vars_to_flat
+from .worker import REFERENCE_MLP_NAMES, flat_to_tf_vars, restricted_assign, tf_vars_to_flat
 
 
 def _dist_env():
@@ -54,6 +55,17 @@ def _mlp_graph(batch, lr):
 def train_mirrored(flags, dataset, log=print, max_steps=None):
     rank, world, local = _dist_env()
     use_gpu = torch.cuda.is_available() and flags.device != "cpu"
+    # --optimizer momentum | adam: inside the fused step on the GPU (train/fused_mlp.py), ops/
+    # optim.py's CPU branches on the autograd path; the slot variables join the checkpoints
+    # under TF's names (global/dense/kernel/Momentum, .../Adam, .../Adam_1, ...)
+    opt_kind = gpu_ps_optim.check_kind(getattr(flags, "optimizer", "sgd"))
+    opt_kw = dict(momentum=float(getattr(flags, "momentum", gpu_ps_optim.DEFAULTS["momentum"])),
+                  beta1=float(getattr(flags, "adam_beta1", gpu_ps_optim.DEFAULTS["beta1"])),
+                  beta2=float(getattr(flags, "adam_beta2", gpu_ps_optim.DEFAULTS["beta2"])),
+                  epsilon=float(getattr(flags, "adam_epsilon", gpu_ps_optim.DEFAULTS["epsilon"])))
+    if opt_kind != "sgd" and getattr(flags, "zero1", False):
+        raise ValueError("--optimizer %s does not support --zero1: the sharded update applies "
+                         "gradient descent only" % opt_kind)
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -108,9 +120,11 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     if use_gpu:
         fused = factor = x_all = None
         pipe = True
-        if comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl":
+        if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
+                and opt_kind == "sgd"):
             # exchange engine (fused into the backward kernel / factor all-gather) when
-            # verified and faster than the all-reduce engine
+            # verified and faster than the all-reduce engine (sgd only: with an optimizer the
+            # all-reduce engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -131,13 +145,15 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              else None, world_size=world, fused_comm=fused, factor_comm=factor,
                              x_all=x_all if factor is not None else None, rank=rank,
                              pipeline=pipe if comm is not None else True,
-                             shuffle=shuffle, shuffle_seed=shuffle_seed)
+                             shuffle=shuffle, shuffle_seed=shuffle_seed, optimizer=opt_kind,
+                             **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
         # eval / replica-check points, because the loop below reads each chunk's stats on
         # EVERY rank (stats_range flushes there, collectively)
         get_params = tr.snapshot
+        get_state = lambda: tr.snapshot(with_slots=True)  # noqa: E731
         step_fn = None
     else:
         model = mlp_model.MnistMLP(flat=params)
@@ -147,6 +163,9 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                 if zero1 else None)
         state["pos"] = 0
         get_params = lambda: model.flat.detach().clone()  # noqa: E731
+        cpu_slots = [torch.zeros(mlp_step.NPARAM)
+                     for _ in range(gpu_ps_optim.num_slots(opt_kind))]
+        get_state = lambda: (get_params(), [t.clone() for t in cpu_slots])  # noqa: E731
 
         def step_fn():
             i = state["pos"]
@@ -176,15 +195,29 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             else:
                 g = model.flat.grad
             with torch.no_grad():
-                optim.sgd_(model.flat.data, g, flags.learning_rate)
+                if opt_kind == "momentum":
+                    optim.momentum_(model.flat.data, g, cpu_slots[0], flags.learning_rate,
+                                    momentum=opt_kw["momentum"])
+                elif opt_kind == "adam":  # t = global_step + 1 of this step
+                    optim.adam_(model.flat.data, g, cpu_slots[0], cpu_slots[1],
+                                flags.learning_rate, i + 1, beta1=opt_kw["beta1"],
+                                beta2=opt_kw["beta2"], eps=opt_kw["epsilon"], weight_decay=0.0,
+                                adamw=False)
+                else:
+                    optim.sgd_(model.flat.data, g, flags.learning_rate)
             return float(loss), float(acc)
 
-    saver = FastSaver({n: None for n in
-                       ("global/dense/kernel", "global/dense/bias", "global/dense_1/kernel",
-                        "global/dense_1/bias", "global/global_step")})
+    # one name tuple per slot plane, kernels in TF layout like the variables themselves
+    slot_names = [tuple(n) for n in gpu_ps_optim.slot_names(opt_kind, REFERENCE_MLP_NAMES)]
+    var_names = (list(REFERENCE_MLP_NAMES) + [n for names in slot_names for n in names]
+                 + ["global/global_step"])
+    saver = FastSaver({n: None for n in var_names})
 
     def save_vars():
-        v = {k: t.contiguous() for k, t in flat_to_tf_vars(get_params().cpu()).items()}
+        p, slots = get_state()
+        v = {k: t.contiguous() for k, t in flat_to_tf_vars(p.cpu()).items()}
+        for names, plane in zip(slot_names, slots):
+            v.update({k: t.contiguous() for k, t in flat_to_tf_vars(plane.cpu(), names).items()})
         v["global/global_step"] = torch.tensor(global_step(), dtype=torch.int32)
         return v
 
@@ -197,15 +230,24 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     def restore(values):
         p = torch.zeros(mlp_step.NPARAM)
         tf_vars_to_flat(values, p)
+        # (a checkpoint that lacks this optimizer's slot variables -- an sgd run's, another
+        # optimizer's -- never gets here: FastSaver.restore raises KeyError over its var list,
+        # as TF's restore and the GPU parameter store's path do)
+        planes = [tf_vars_to_flat(values, torch.zeros(mlp_step.NPARAM), names)
+                  for names in slot_names]
         if use_gpu:
             tr.load_params(p.to(dev))
+            tr.load_slots([t.to(dev) for t in planes])
             tr.seek(int(values["global/global_step"]))
         else:
             model.flat.data.copy_(p)
+            for d, t in zip(cpu_slots, planes):
+                d.copy_(t)
             state["pos"] = int(values["global/global_step"])
         state["step"] = int(values["global/global_step"])
 
-    saver.assign = restore
+    # (the var list only: an sgd run restoring a momentum / Adam checkpoint ignores the slots)
+    saver.assign = restricted_assign(restore, var_names)
     # checkpoints are taken by the training loop between chunks (Supervisor.service): the
     # fused trainer's deferred update may only be flushed where every rank flushes it
     sv = Supervisor(is_chief=is_chief, logdir=flags.logdir if is_chief else None,
@@ -253,11 +295,18 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             s = torch.tensor([global_step()], dtype=torch.int64)
             dist.broadcast(s, 0)
             s = int(s.item())
+            planes = [t.clone() for t in (tr.slots if use_gpu else cpu_slots)]
+            if comm is not None:  # (a restored chief's slot planes)
+                for t in planes:
+                    comm.broadcast_(t, 0)
             if use_gpu:
                 tr.load_params(p)
+                tr.load_slots(planes)
                 tr.seek(s)
             else:
                 model.flat.data.copy_(p)
+                for d, t in zip(cpu_slots, planes):
+                    d.copy_(t)
                 state["pos"] = s
         chunk = int(flags.log_every)
         state["step"] = global_step()

@@ -53,10 +53,20 @@ def main(argv=None):
 
         return eval_job(FLAGS)
     if FLAGS.strategy == "mirrored" and FLAGS.optimizer != "sgd":
-        # --optimizer momentum | adam: the GPU parameter store's (train/worker.py validates the
-        # ps_async combinations); never silently ignored
-        raise SystemExit("--optimizer %s needs --strategy ps_async --ps_device gpu"
-                         % FLAGS.optimizer)
+        # --optimizer momentum | adam: the fused MLP trainer's and the GPU parameter store's
+        # (train/worker.py validates the ps_async combinations); never silently ignored
+        from distributedtensorflowexample_amd.parallel.gpu_ps_optim import check_kind
+
+        try:
+            check_kind(FLAGS.optimizer)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        if FLAGS.model != "mlp":
+            raise SystemExit("--optimizer %s needs --model mlp under --strategy mirrored (or "
+                             "--strategy ps_async --ps_device gpu)" % FLAGS.optimizer)
+        if getattr(FLAGS, "zero1", False):
+            raise SystemExit("--optimizer %s does not support --zero1: the sharded update "
+                             "applies gradient descent only" % FLAGS.optimizer)
     if FLAGS.strategy == "mirrored" and FLAGS.model != "mlp":
         from distributedtensorflowexample_amd.train.mirrored_mlp import shutdown_mirrored
         from distributedtensorflowexample_amd.train.mirrored_models import train_model_mirrored
