@@ -48,6 +48,16 @@
 //   those slab stores written through (sc1): the boundary to the head shrinks by what the
 //     stores' own drain adds to the launch's tail, no gain per step;
 //   p_new written through as well: slower in the driver-sized run.
+// The lean head reads its 28 slab planes through ONE buffer descriptor (head_row<.., SB>,
+// profiles/lean_prologue/: -0.24 us per step, bit-identical results): lane offset in the vector
+// offset, plane and row in the scalar one, so the one in-order wave issues 28 loads with a scalar
+// add each where the pointer form rebuilt a 64-bit per-lane address for every plane (48 VALU
+// adds and 24 s_nop between the first and the last slab load).  Measured and not kept there:
+//   b1 / W2 / b2 through a descriptor as well (no VALU ahead of the last operand load at all)
+//     and 1 / B computed behind the head's operand loads instead of ahead of them: within the
+//     noise;
+//   the first launch's dz1R / x_prev loads through descriptors with 32-bit offsets (no 64-bit
+//     multiply-add ahead of the last phase-A operand): within the noise.
 // Momentum and Adam live in that first launch too (mlp_lean_fwdapply_opt_kernel, OptArgs below):
 // the lane that owns a parameter element also owns its slot values, so no gradient buffer and no
 // optimizer launch exist; the SGD instantiations are unchanged (profiles/fused_optim/).
@@ -336,7 +346,8 @@ __device__ __forceinline__ void head_allgather(const MlpXg& xg, unsigned ep, int
 // compiler and carry no ordering against the fence, so the b1 / W2 / b2 loads go through a
 // laundered global pointer: ordinary loads, which stay in front of it.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false, int NGT = 0>
+template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false, int NGT = 0,
+          bool SB = false>
 __device__ __forceinline__ void head_row(
     const int row, const int lane, const float* __restrict__ p_old,
     const float* __restrict__ grad, float lr, float* __restrict__ p_new,
@@ -344,10 +355,14 @@ __device__ __forceinline__ void head_row(
     const MlpXg& xg, float* __restrict__ dz1A) {
   static_assert(XW == 0 || (!APPLY && !TRACE), "the factor exchange runs the direct step");
   static_assert(!RM || (XW == 0 && !APPLY), "row-major factors: the single-GPU two-launch step");
+  static_assert(!SB || (RM && NSLAB == KS3), "slab loads through a descriptor: the lean head");
   if (TRACE) trace_stamp(tr, row * 4 + 0);
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
   const int y = labels[row];
-  float invB = 1.f / (float)B;  // (an IEEE division sequence: pinned here, under the memory wait)
+  // (an IEEE division sequence of 13 instructions; the asm pins it HERE, which in the ISA is
+  // ahead of every operand load, not under the memory wait.  Computed behind the loads' fence
+  // instead it measured the same: profiles/lean_prologue/)
+  float invB = 1.f / (float)B;
   asm volatile("" : "+v"(invB));
   const unsigned ep = XW > 0 ? xg.epochs[MLP_XG_HEAD_EPOCH + row] + 1 : 0u;
   const bool publish = APPLY && row == 0;
@@ -368,9 +383,25 @@ __device__ __forceinline__ void head_row(
     jj[u] = j0 + u;
   }
   f32x2 sv[NSLAB];
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  if constexpr (SB) {
+    // ONE descriptor over the slab planes, built from wave-uniform values (the workspace base, a
+    // kernel argument, and BP); the lane's j0 * 4 is the vector offset, plane and row the scalar
+    // one: 28 buffer loads with one s_add each between them.  The pointer form keeps a 64-bit
+    // address per lane and rebuilds it for every plane (the plane stride, BP * HP * 4, fits no
+    // immediate offset): two VALU adds, an s_mov and an s_nop per load of the one in-order wave.
+    const __amdgpu_buffer_rsrc_t sr = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)w.slab, (short)0, NSLAB * BP * HP * 4, 0x00020000);
+#pragma unroll
+    for (int s = 0; s < NSLAB; ++s) {
+      const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(sr, j0 * 4, (s * BP + row) * HP * 4, 0);
+      sv[s] = f32x2{__uint_as_float(v.x), __uint_as_float(v.y)};
+    }
+  } else {
 #pragma unroll
   for (int s = 0; s < NSLAB; ++s)
     sv[s] = *reinterpret_cast<const f32x2*>(&w.slab[((size_t)s * BP + row) * HP + j0]);
+  }
   typedef const __attribute__((address_space(1))) float* gcf;
   typedef const __attribute__((address_space(1))) f32x2* gcf2;
   unsigned long long pa = (unsigned long long)p_old;
@@ -1663,8 +1694,8 @@ __device__ __forceinline__ void lean_head_body(const float* __restrict__ p,
                                                float* __restrict__ ws, int B,
                                                unsigned long long* __restrict__ tr) {
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
-  head_row<false, TRACE, 0, KS3, true, NGT>(blockIdx.x, threadIdx.x, p, p, 0.f, nullptr, labels, w,
-                                            B, tr, MlpXg{}, nullptr);
+  head_row<false, TRACE, 0, KS3, true, NGT, true>(blockIdx.x, threadIdx.x, p, p, 0.f, nullptr,
+                                                  labels, w, B, tr, MlpXg{}, nullptr);
 }
 
 template <int NGT>
