@@ -52,7 +52,10 @@ struct MlpOpt {
   float *s0, *s1;
   int* tp;
   float h0, h1, h2;
+  int sched = 0;          // != 0: the scheduled instantiations (tp heads the 8-word schedule block)
+  float* lrs = nullptr;   // their rate ring
 };
+void mlp_lr_sched_launch(const int*, const int*, float, float*, float*, int, hipStream_t);
 void mlp_lean_fwdapply_opt_launch(const float*, float*, float, const float*, const float*, float*,
                                   int*, float*, int, int, int, int, const MlpOpt&, hipStream_t);
 void mlp_apply_opt_launch(const float*, float*, float, const float*, float*, int*, float*, int,
@@ -289,6 +292,37 @@ PYBIND11_MODULE(_hip, m) {
         P<int>(ctr), P<float>(stats), ring, B, par,
         dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1, h2}, S(s));
   }, "the flush of mlp_lean_fwdapply_opt: the pending update alone, p_old -> p_new");
+  // The same two launches with a learning-rate schedule evaluated on the device
+  // (ops/lr_schedule.py): kind 0 (sgd), 1, 2; blk: the int32[8] schedule block whose first two
+  // words are the step pair; lr: the base rate; lrs: the f32 rate ring (length `ring`), or 0.
+  m.def("mlp_lean_fwdapply_sched", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                                      uintptr_t x, uintptr_t ws, uintptr_t ctr, uintptr_t stats,
+                                      int ring, int B, int apply, int par, int kind, uintptr_t s0,
+                                      uintptr_t s1, uintptr_t blk, float h0, float h1, float h2,
+                                      uintptr_t lrs, uintptr_t s) {
+    dtfx::mlp_lean_fwdapply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<const float>(x),
+        P<float>(ws), P<int>(ctr), P<float>(stats), ring, B, apply, par,
+        dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(blk), h0, h1, h2, 1, P<float>(lrs)},
+        S(s));
+  }, "mlp_lean_fwdapply_opt with the rate of the applied step computed in the kernel from the "
+     "schedule block (and published to the rate ring)");
+  m.def("mlp_apply_sched", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                              uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B,
+                              int par, int kind, uintptr_t s0, uintptr_t s1, uintptr_t blk,
+                              float h0, float h1, float h2, uintptr_t lrs, uintptr_t s) {
+    dtfx::mlp_apply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<float>(ws),
+        P<int>(ctr), P<float>(stats), ring, B, par,
+        dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(blk), h0, h1, h2, 1, P<float>(lrs)},
+        S(s));
+  }, "the flush of mlp_lean_fwdapply_sched");
+  m.def("mlp_lr_sched", [](uintptr_t ctr, uintptr_t blk, float lr0, uintptr_t out, uintptr_t lrs,
+                           int ring, uintptr_t s) {
+    dtfx::mlp_lr_sched_launch(P<const int>(ctr), P<const int>(blk), lr0, P<float>(out),
+                              P<float>(lrs), ring, S(s));
+  }, "one wave: the scheduled rate of step ctr - 1 into out[0] (ops.optim's lr_tensor) and, with "
+     "lrs != 0, into the rate ring");
   struct MlpRunOptPlan {
     float *p0, *p1;
     const float* x;
@@ -308,6 +342,15 @@ PYBIND11_MODULE(_hip, m) {
                              nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B,
                              dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1,
                                           h2}};
+      }))
+      .def(py::init([](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
+                       uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int kind,
+                       uintptr_t s0, uintptr_t s1, uintptr_t blk, float h0, float h1, float h2,
+                       uintptr_t lrs) {  // the scheduled form (mlp_lean_fwdapply_sched)
+        return MlpRunOptPlan{P<float>(p0), P<float>(p1), P<const float>(x), P<const int>(lab),
+                             nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B,
+                             dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(blk), h0, h1,
+                                          h2, 1, P<float>(lrs)}};
       }))
       .def("run", [](const MlpRunOptPlan& p, int cur, int pending, float lr, int pos, int n,
                      int flush, uintptr_t s) {

@@ -61,6 +61,10 @@
 // Momentum and Adam live in that first launch too (mlp_lean_fwdapply_opt_kernel, OptArgs below):
 // the lane that owns a parameter element also owns its slot values, so no gradient buffer and no
 // optimizer launch exist; the SGD instantiations are unchanged (profiles/fused_optim/).
+// Learning-rate schedules (sched_rate, mlp_lean_fwdapply_sched_kernel): scheduled instantiations
+// of that entry point -- sgd among them -- compute the rate of the step they apply from the step
+// word and an 8-word schedule block, once per wave, and the stats lane publishes it to a rate
+// ring; the constant-rate kernels are unchanged (profiles/lr_schedule/: +0.03 .. +0.2 us a step).
 //
 // All MFMA work is v_mfma_f32_16x16x4_f32 (exact f32).  Lane l supplies
 // A[i = l&15][k = l>>4], B[k = l>>4][j = l&15]; C[row = (l>>4)*4 + r][col = l&15].
@@ -823,13 +827,50 @@ struct OptArgs {
   int* tp;
   float h0, h1, h2;  // momentum: mu; adam: beta1, beta2, epsilon
   int apply, par;
+  float* lrs;        // SCHED: the rate ring (f32 [stats_ring], parallel to the stats ring), or null
 };
+// Learning-rate schedules evaluated on the device (the SCHED instantiations; ops/lr_schedule.py
+// is the definition, its value_f32 this arithmetic operation for operation).  The step pair is
+// then the head of an 8-word block [tp0, tp1, kind | staircase << 2, decay_steps, a, inv_decay,
+// inv_warmup, 0], 32-byte aligned.  a = f32(log2 decay_rate) (exponential) or decay_rate (inverse
+// time); inv_warmup = 0 skips the warm-up.  s: the 0-based global_step of the step applied.
+// Wave-uniform: the whole block is fetched at once (sched_load: every word unconditionally, so
+// the wave makes ONE round trip instead of one per word a branch happens to need) and a handful
+// of scalar-side operations follow, every alternative computed and selected.
+//   staircase q: integer division of the step word (float(s) * f32(1 / 3) misses exact multiples)
+//   exponential: exp2(q * log2 rate) on the transcendental unit, as opt_coef's b^t
+enum : int { SCHED_CONSTANT = 0, SCHED_EXPONENTIAL = 1, SCHED_INVERSE_TIME = 2 };
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+struct SchedBlock {
+  i32x4 lo, hi;  // lo = {tp0, tp1, flags, decay_steps}, hi = {a, inv_decay, inv_warmup, 0}
+};
+__device__ __forceinline__ SchedBlock sched_load(const int* __restrict__ blk) {
+  return {*reinterpret_cast<const i32x4*>(blk), *reinterpret_cast<const i32x4*>(blk + 4)};
+}
+__device__ __forceinline__ float sched_rate(float lr0, int s, const SchedBlock& w) {
+  const int kind = w.lo.z & 3, stair = (w.lo.z >> 2) & 1;
+  const unsigned ds = (unsigned)w.lo.w;
+  const float a = __int_as_float(w.hi.x), inv_ds = __int_as_float(w.hi.y);
+  const float inv_warm = __int_as_float(w.hi.z);
+  const float qi = (float)((unsigned)s / ds), qf = (float)s * inv_ds;
+  const float q = stair ? qi : qf;
+  const float e = __builtin_amdgcn_exp2f(q * a);
+  const float r = __builtin_amdgcn_rcpf(__builtin_fmaf(a, q, 1.f));
+  const float decay = kind == SCHED_EXPONENTIAL ? e : kind == SCHED_INVERSE_TIME ? r : 1.f;
+  const float lr = lr0 * decay;
+  const float warm = fminf(1.f, (float)(s + 1) * inv_warm);
+  return inv_warm > 0.f ? lr * warm : lr;
+}
 // momentum: lr, h0 = mu.  adam: lr = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t)
 struct OptCoef {
   float lr, h0, h1, h2, rbc2;
 };
-template <int OPT>
+template <int OPT, bool SCHED = false>
 __device__ __forceinline__ OptCoef opt_coef(float lr, const OptArgs& oa) {
+  if constexpr (SCHED) {  // the applied step's rate
+    const SchedBlock w = sched_load(oa.tp);
+    lr = sched_rate(lr, oa.par ? w.lo.y : w.lo.x, w);
+  }
   OptCoef c = {lr, oa.h0, oa.h1, oa.h2, 1.f};
   if constexpr (OPT == OPT_ADAM) {  // (wave-uniform: once per wave, not per element)
     // b^t = exp2(t log2 b) on the transcendental unit: 0 <= b < 1, so the product is <= 0, and
@@ -846,7 +887,9 @@ __device__ __forceinline__ OptCoef opt_coef(float lr, const OptArgs& oa) {
 template <int OPT>
 __device__ __forceinline__ float opt_update(float p, float g, float& s0, float& s1,
                                             const OptCoef& c) {
-  if constexpr (OPT == OPT_MOMENTUM) {
+  if constexpr (OPT == OPT_SGD) {  // (scheduled gradient descent: the SGD step's own expression)
+    return p - c.lr * g;
+  } else if constexpr (OPT == OPT_MOMENTUM) {
     s0 = c.h0 * s0 + g;
     return p - c.lr * s0;
   } else {
@@ -869,7 +912,7 @@ __device__ __forceinline__ float opt_update(float p, float g, float& s0, float& 
 // OPT (the lean step's optimizer variants; DIRECT, no exchange): the owning lane also reads and
 // rewrites its slot values (addresses clamped like p_src's, stores behind the p store's
 // predicate and oa.apply); the stats lane hands the step word on (tp[par ^ 1]).
-template <bool DIRECT, int NGT, int XW, bool RM = false, int OPT = OPT_SGD>
+template <bool DIRECT, int NGT, int XW, bool RM = false, int OPT = OPT_SGD, bool SCHED = false>
 __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx,
                                             float* __restrict__ p, float lr,
                                             float* __restrict__ grad, const Bufs& w,
@@ -877,7 +920,8 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
                                             int stats_ring, int B, const MlpXg& xg,
                                             const float* __restrict__ p_src = nullptr,
                                             int stats_on = 1, const OptArgs& oa = OptArgs{}) {
-  static_assert(OPT == OPT_SGD || (DIRECT && XW == 0), "optimizer variants: the lean step only");
+  constexpr bool OX = OPT != OPT_SGD || SCHED;  // the OptArgs path (scheduled sgd: no slots)
+  static_assert(!OX || (DIRECT && XW == 0), "optimizer variants: the lean step only");
   if (p_src == nullptr) p_src = p;
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
   const int NG = NGT > 0 ? NGT : BP / 16;
@@ -894,8 +938,11 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   int role = wave;  // 0 / 2 (SPLIT): dW2 (halves), 1: db1, 2 (!SPLIT): db2, 3: stats (+ db2)
   if (wave == 3) {
     if (jt != 0) return;
-    if constexpr (OPT != OPT_SGD) {  // the next launch's step word (this one reads tp[par])
-      if (lane == 0) oa.tp[oa.par ^ 1] = oa.tp[oa.par] + (stats_on ? 1 : 0);
+    [[maybe_unused]] float rate = 0.f;  // SCHED: the rate of the step this launch applies
+    if constexpr (OX) {  // the next launch's step word (this one reads tp[par])
+      const int s = oa.tp[oa.par];
+      if constexpr (SCHED) rate = sched_rate(lr, s, sched_load(oa.tp));
+      if (lane == 0) oa.tp[oa.par ^ 1] = s + (stats_on ? 1 : 0);
     }
     if (stats_on) {
       float l = 0.f, a = 0.f;
@@ -911,6 +958,9 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
           float* st = stats + (size_t)(step % stats_ring) * 2;
           st[0] = l / (float)B;
           st[1] = a / (float)B;
+        }
+        if constexpr (SCHED) {
+          if (oa.lrs) oa.lrs[step % stats_ring] = rate;
         }
         *ctr = step + 1;
       }
@@ -981,7 +1031,7 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   (void)db2;
   __builtin_amdgcn_sched_barrier(0);
   [[maybe_unused]] OptCoef oc = {};  // (adam's b1^t / b2^t while the loads are in flight)
-  if constexpr (OPT != OPT_SGD) oc = opt_coef<OPT>(lr, oa);
+  if constexpr (OX) oc = opt_coef<OPT, SCHED>(lr, oa);
   // NB: padded batch columns of dz1T/dlT are zero, so multiplying by 1 is exact.
   f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
 #pragma unroll
@@ -1035,16 +1085,18 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
       xg_exchange<XW>(xg, ep, off, ok, v, fail);
     }
   }
-  if constexpr (OPT != OPT_SGD) {
+  if constexpr (OX) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // (computed by every lane and selected: oa.apply == 0 copies p and leaves the slots)
       const float pn = opt_update<OPT>(pv[i], v[i], sa[i], sb[i], oc);
       if (ok[i]) {
         p[off[i]] = oa.apply ? pn : pv[i];
-        if (oa.apply) {
-          oa.s0[off[i]] = sa[i];
-          if constexpr (OPT == OPT_ADAM) oa.s1[off[i]] = sb[i];
+        if constexpr (OPT != OPT_SGD) {
+          if (oa.apply) {
+            oa.s0[off[i]] = sa[i];
+            if constexpr (OPT == OPT_ADAM) oa.s1[off[i]] = sb[i];
+          }
         }
       }
     }
@@ -1212,7 +1264,7 @@ __global__ __launch_bounds__(256) void mlp_wgrad_kernel(
 // computed by every lane and selected by oa.apply (no branch around the loads' uses, which
 // would let the compiler sink them below the barrier).
 template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true,
-          bool ORD = false, bool A16 = false, int OPT = OPT_SGD>
+          bool ORD = false, bool A16 = false, int OPT = OPT_SGD, bool SCHED = false>
 __device__ __forceinline__ void fwdapply_block(
     const int bid, const float* __restrict__ p_old, float* __restrict__ p_new, float lr,
     const float* __restrict__ x_prev, const float* __restrict__ x, const Bufs& w,
@@ -1221,7 +1273,8 @@ __device__ __forceinline__ void fwdapply_block(
     unsigned long long* __restrict__ trs = nullptr, const OptArgs& oa = OptArgs{}) {
   static_assert(!ORD || (XW == 0 && KSX == KS3), "load order of the row-quad form");
   static_assert(!A16 || ORD, "the 16-byte apply belongs to the lean step");
-  static_assert(OPT == OPT_SGD || (A16 && !TRACE), "optimizer variants: the lean step only");
+  constexpr bool OX = OPT != OPT_SGD || SCHED;  // the OptArgs path (scheduled sgd: no slots)
+  static_assert(!OX || (A16 && !TRACE), "optimizer variants: the lean step only");
   // stamps per wave: 0 entry, 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab
   // stored; with XW > 0 also 4 local gradient slice ready (exchange starts), 5 two-shot: the
   // owned sums done (first hop), 6 exchange done -- 8 slots per wave then
@@ -1243,9 +1296,9 @@ __device__ __forceinline__ void fwdapply_block(
   constexpr bool RM = XW == 0 && KSX == KS3;
   if (bid >= HT * KSX) {
     const int jt = bid - HT * KSX;
-    if constexpr (OPT != OPT_SGD)
-      wgrad_small<true, NGT, XW, RM, OPT>(jt, wave, lane, 0, p_new, lr, nullptr, w, ctr, stats,
-                                          stats_ring, B, xg, p_old, stats_on, oa);
+    if constexpr (OX)
+      wgrad_small<true, NGT, XW, RM, OPT, SCHED>(jt, wave, lane, 0, p_new, lr, nullptr, w, ctr,
+                                                 stats, stats_ring, B, xg, p_old, stats_on, oa);
     else
     wgrad_small<true, NGT, XW, RM>(jt, wave, lane, MLP_XG_SMALL_EPOCH + jt * 4 + wave, p_new, lr,
                                nullptr, w, ctr, stats, stats_ring, B, xg, p_old, stats_on);
@@ -1339,7 +1392,7 @@ __device__ __forceinline__ void fwdapply_block(
     __builtin_amdgcn_sched_barrier(0);  // all loads in flight together
     // (OPT: adam's b1^t / b2^t while the loads are in flight, not between the sum and the store)
     [[maybe_unused]] OptCoef oc = {};
-    if constexpr (OPT != OPT_SGD) oc = opt_coef<OPT>(lr, oa);
+    if constexpr (OX) oc = opt_coef<OPT, SCHED>(lr, oa);
     if constexpr (TRACE && NGT > 0 && FWD) {
       if (trs) {  // loads issued after the first class: ORD pw + xa, else pw + the factors
         unsigned long long* t2 = trs + (size_t)(bid * 4 + wave) * 2;
@@ -1373,17 +1426,19 @@ __device__ __forceinline__ void fwdapply_block(
       }
       const bool live = jw < H;
       float4 v;
-      if constexpr (OPT != OPT_SGD) {
+      if constexpr (OX) {
         v.x = opt_update<OPT>(pw4.x, part.x, sa4.x, sb4.x, oc);
         v.y = opt_update<OPT>(pw4.y, part.y, sa4.y, sb4.y, oc);
         v.z = opt_update<OPT>(pw4.z, part.z, sa4.z, sb4.z, oc);
         v.w = opt_update<OPT>(pw4.w, part.w, sa4.w, sb4.w, oc);
         if (!oa.apply) v = pw4;  // nothing pending: a copy, and no slot byte is written
-        if (oa.apply && lane < IPW && live) {
-          float* so = oa.s0 + OFF_W1 + (size_t)jw * D + f0 + 4 * mw;
-          *reinterpret_cast<float4*>(so) = sa4;
-          if constexpr (OPT == OPT_ADAM)
-            *reinterpret_cast<float4*>(oa.s1 + (so - oa.s0)) = sb4;
+        if constexpr (OPT != OPT_SGD) {
+          if (oa.apply && lane < IPW && live) {
+            float* so = oa.s0 + OFF_W1 + (size_t)jw * D + f0 + 4 * mw;
+            *reinterpret_cast<float4*>(so) = sa4;
+            if constexpr (OPT == OPT_ADAM)
+              *reinterpret_cast<float4*>(oa.s1 + (so - oa.s0)) = sb4;
+          }
         }
       } else {
       v.x = pw4.x - lr * part.x, v.y = pw4.y - lr * part.y;
@@ -1637,7 +1692,7 @@ __global__ __launch_bounds__(256) void mlp_fwdapply_kernel(
 // The data-parallel engines, mlp_fwdapply_launch / mlp_head2_launch and the opt-in fused flush
 // keep mlp_fwdapply_kernel / mlp_head_kernel.
 
-template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD>
+template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD, bool SCHED = false>
 __device__ __forceinline__ void lean_fwdapply_body(
     const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
     const float* __restrict__ x, float* __restrict__ ws, int* __restrict__ ctr,
@@ -1645,8 +1700,8 @@ __device__ __forceinline__ void lean_fwdapply_body(
     unsigned long long* __restrict__ trs, const OptArgs& oa = OptArgs{}) {
   const int B = flags & 511, stats_on = (flags >> 9) & 1, stats_ring = flags >> 10;
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
-  if constexpr (OPT != OPT_SGD)
-    fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT>(
+  if constexpr (OPT != OPT_SGD || SCHED)
+    fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT, SCHED>(
         blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{},
         tr, trs, oa);
   else
@@ -1677,6 +1732,36 @@ __global__ __launch_bounds__(256) void mlp_lean_fwdapply_opt_kernel(
   const OptArgs oa = {s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1};
   lean_fwdapply_body<NGT, false, FWD, OPT>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags,
                                            nullptr, nullptr, oa);
+}
+
+// The scheduled instantiations (sched_rate): the optimizer kernel's arguments -- tp heads the
+// 8-word schedule block, lr is the base rate -- and the rate ring.  OPT_SGD here is scheduled
+// gradient descent: the step pair and the explicit apply bit, no slot planes.
+template <int NGT, bool FWD, int OPT>
+__global__ __launch_bounds__(256) void mlp_lean_fwdapply_sched_kernel(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, float lr, int flags,
+    int* __restrict__ ctr, float* __restrict__ stats, float* __restrict__ s0,
+    float* __restrict__ s1, int* __restrict__ tp, float h0, float h1, float h2, int oflags,
+    float* __restrict__ lrs) {
+  const OptArgs oa = {s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1, lrs};
+  lean_fwdapply_body<NGT, false, FWD, OPT, true>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags,
+                                                 nullptr, nullptr, oa);
+}
+
+// The all-reduce engine's rate (FusedMLPTrainer._apply_reduced): one wave writes lr(s) of the
+// pending step -- s = ctr - 1: the step that produced the gradient has advanced the counter --
+// into a device float that ops.optim's lr_tensor reads, and into the rate ring (lrs may be null).
+__global__ __launch_bounds__(64) void mlp_lr_sched_kernel(const int* __restrict__ ctr,
+                                                          const int* __restrict__ blk, float lr0,
+                                                          float* __restrict__ out,
+                                                          float* __restrict__ lrs, int ring) {
+  const int s = *ctr - 1;
+  const float rate = sched_rate(lr0, s, sched_load(blk));
+  if (threadIdx.x == 0) {
+    *out = rate;
+    if (lrs && s >= 0) lrs[s % ring] = rate;
+  }
 }
 
 template <int NGT>
@@ -2790,21 +2875,37 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
 // tp[par ^ 1], so consecutive launches must alternate it (as they alternate the buffers).
 // Only the lean 28-slice step has these variants: DTFX_MLP_KS=14 and the fused flush
 // (DTFX_MLP_FLUSH_FUSED) are refused.
+// sched != 0: the scheduled instantiations (mlp_lean_fwdapply_sched_kernel) -- tp then heads the
+// 8-word schedule block, lr is the base rate, lrs the rate ring (f32 [stats_ring], or null), and
+// kind 0 is scheduled gradient descent (no slot planes).
 struct MlpOpt {
   int kind;
   float *s0, *s1;
   int* tp;
   float h0, h1, h2;
+  int sched = 0;
+  float* lrs = nullptr;
 };
 
 static void check_opt(const MlpOpt& o, const char* who) {
   const std::string w(who);
-  if (o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
-    throw std::runtime_error(w + ": optimizer kind must be 1 (momentum) or 2 (adam)");
-  if (mlp_single_ks() != mlp::KS3)
-    throw std::runtime_error(w + ": DTFX_MLP_KS=14 has no optimizer variant (sgd only)");
-  if (!o.s0 || !o.tp || (o.kind == mlp::OPT_ADAM && !o.s1))
-    throw std::runtime_error(w + ": null slot plane / step pair");
+  if (o.sched) {  // (scheduled gradient descent is kind 0 and has no slot plane)
+    if (o.kind != mlp::OPT_SGD && o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
+      throw std::runtime_error(w + ": scheduled optimizer kind must be 0 (sgd), 1 or 2");
+    if (mlp_single_ks() != mlp::KS3)
+      throw std::runtime_error(w + ": DTFX_MLP_KS=14 has no learning-rate schedule variant");
+    if (!o.tp || (o.kind != mlp::OPT_SGD && !o.s0) || (o.kind == mlp::OPT_ADAM && !o.s1))
+      throw std::runtime_error(w + ": null slot plane / schedule block");
+    if (reinterpret_cast<uintptr_t>(o.tp) & 31)
+      throw std::runtime_error(w + ": the schedule block must be 32-byte aligned");
+  } else {
+    if (o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
+      throw std::runtime_error(w + ": optimizer kind must be 1 (momentum) or 2 (adam)");
+    if (mlp_single_ks() != mlp::KS3)
+      throw std::runtime_error(w + ": DTFX_MLP_KS=14 has no optimizer variant (sgd only)");
+    if (!o.s0 || !o.tp || (o.kind == mlp::OPT_ADAM && !o.s1))
+      throw std::runtime_error(w + ": null slot plane / step pair");
+  }
   if ((reinterpret_cast<uintptr_t>(o.s0) | reinterpret_cast<uintptr_t>(o.s1)) & 15)
     throw std::runtime_error(w + ": slot planes must be 16-byte aligned");
 }
@@ -2824,14 +2925,30 @@ static void lean_first_opt_launch(const float* p_old, float* p_new, float lr, co
   hipLaunchKernelGGL((mlp_lean_fwdapply_opt_kernel<NGT, FWD, OPTK>), grid, block, 0, stream,     \
                      p_old, p_new, x_prev, x, ws, lr, flags, ctr, stats, o.s0, o.s1, o.tp, o.h0, \
                      o.h1, o.h2, oflags)
+#define DTFX_LS(NGT, OPTK)                                                                       \
+  hipLaunchKernelGGL((mlp_lean_fwdapply_sched_kernel<NGT, FWD, OPTK>), grid, block, 0, stream,   \
+                     p_old, p_new, x_prev, x, ws, lr, flags, ctr, stats, o.s0, o.s1, o.tp, o.h0, \
+                     o.h1, o.h2, oflags, o.lrs)
   const bool rt7 = (B + 15) / 16 == 7;
-  if (o.kind == OPT_MOMENTUM) {
+  if (o.sched) {
+    if (o.kind == OPT_SGD) {
+      if (rt7) DTFX_LS(7, OPT_SGD);
+      else DTFX_LS(0, OPT_SGD);
+    } else if (o.kind == OPT_MOMENTUM) {
+      if (rt7) DTFX_LS(7, OPT_MOMENTUM);
+      else DTFX_LS(0, OPT_MOMENTUM);
+    } else {
+      if (rt7) DTFX_LS(7, OPT_ADAM);
+      else DTFX_LS(0, OPT_ADAM);
+    }
+  } else if (o.kind == OPT_MOMENTUM) {
     if (rt7) DTFX_LO(7, OPT_MOMENTUM);
     else DTFX_LO(0, OPT_MOMENTUM);
   } else {
     if (rt7) DTFX_LO(7, OPT_ADAM);
     else DTFX_LO(0, OPT_ADAM);
   }
+#undef DTFX_LS
 #undef DTFX_LO
 }
 
@@ -2877,8 +2994,9 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
       pos >= nbatches || n < 0 || (cur != 0 && cur != 1))
     throw std::runtime_error("mlp_run_pipelined_opt: bad buffers / position / count");
   if (flush && mlp_flush_fused())
-    throw std::runtime_error("mlp_run_pipelined_opt: the fused flush (DTFX_MLP_FLUSH_FUSED) has "
-                             "no optimizer variant (sgd only)");
+    throw std::runtime_error(
+        std::string("mlp_run_pipelined_opt: the fused flush (DTFX_MLP_FLUSH_FUSED) has ") +
+        (o.sched ? "no learning-rate schedule variant" : "no optimizer variant (sgd only)"));
   float* bufs[2] = {p0, p1};
   const size_t xb = (size_t)B * D;
   for (int i = 0; i < n; ++i) {
@@ -2898,6 +3016,17 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
                                  x + (size_t)prev * xb, ws, ctr, stats, stats_ring, B, 1, cur, o,
                                  stream);
   }
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// The all-reduce engine's scheduled rate (mlp_lr_sched_kernel): lr(ctr - 1) -> out[0] and, with
+// lrs, the rate ring.  blk: the 8-word schedule block (32-byte aligned).
+void mlp_lr_sched_launch(const int* ctr, const int* blk, float lr0, float* out, float* lrs,
+                         int ring, hipStream_t stream) {
+  if (!ctr || !blk || !out || (reinterpret_cast<uintptr_t>(blk) & 31) || (lrs && ring < 1))
+    throw std::runtime_error("mlp_lr_sched: needs ctr, a 32-byte aligned schedule block, out");
+  hipLaunchKernelGGL(mlp::mlp_lr_sched_kernel, dim3(1), dim3(64), 0, stream, ctr, blk, lr0, out,
+                     lrs, lrs ? ring : 1);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

@@ -214,6 +214,21 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_float("adam_beta1", 0.9, "--optimizer adam: beta1", fv)
     DEFINE_float("adam_beta2", 0.999, "--optimizer adam: beta2", fv)
     DEFINE_float("adam_epsilon", 1e-8, "--optimizer adam: epsilon", fv)
+    DEFINE_string("lr_schedule", "constant",
+                  "constant | exponential (tf.train.exponential_decay) | inverse_time "
+                  "(tf.train.inverse_time_decay) of --learning_rate over global_step.  "
+                  "--strategy mirrored, --model mlp only: evaluated on the device inside the "
+                  "fused two-launch step (one GPU), by the all-reduce engine (several) or on the "
+                  "autograd path (--device cpu); ps_async, --model bert|resnet50 and --zero1 "
+                  "train at a constant rate and refuse it", fv)
+    DEFINE_integer("lr_decay_steps", 1000, "--lr_schedule: decay_steps (>= 1)", fv)
+    DEFINE_float("lr_decay_rate", 0.96, "--lr_schedule: decay_rate (> 0)", fv)
+    DEFINE_boolean("lr_staircase", False,
+                   "--lr_schedule: decay at whole multiples of --lr_decay_steps "
+                   "(global_step // decay_steps)", fv)
+    DEFINE_integer("lr_warmup_steps", 0,
+                   "linear warm-up: the rate of step s is scaled by min(1, (s + 1) / "
+                   "lr_warmup_steps); 0 = none (also with --lr_schedule constant)", fv)
     DEFINE_string("cpu_affinity", "numa",
                   "async PS: numa = the ps tasks on GPU 0's NUMA node (--numa_node overrides), "
                   "8 cores each; worker i on 2 cores of its OWN GPU's node, after the ps tasks' "

@@ -178,21 +178,38 @@ class PipelinedOpt:
     parameter layout, updated in place by the lane that owns each element; ``tp`` -- the int32
     [2] step pair (a launch of buffer parity ``par`` reads ``tp[par]`` = global_step of the step
     it applies, Adam's ``t - 1``, and writes ``tp[par ^ 1]``); ``hyper`` --
-    ``gpu_ps_optim.hyper_args``' three words."""
+    ``gpu_ps_optim.hyper_args``' three words.
+
+    ``schedule`` (an ``ops.lr_schedule.LRSchedule``): the scheduled instantiations
+    (``mlp_lean_fwdapply_sched``).  The step pair then heads ``block``, the int32 [8] device block
+    ``[tp0, tp1, kind | staircase << 2, decay_steps, a, inv_decay_steps, inv_warmup, 0]`` that a
+    wave fetches at once (``tp`` stays an int32 [2] view of it), ``rates`` is the f32 rate ring
+    parallel to the stats ring (index ``step % stats_ring``), and kind ``"sgd"`` is allowed:
+    scheduled gradient descent has the step pair and no slot plane."""
 
     KINDS = {"momentum": 1, "adam": 2}
 
-    def __init__(self, kind, device, momentum=0.9, beta1=0.9, beta2=0.999, epsilon=1e-8):
+    def __init__(self, kind, device, momentum=0.9, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                 schedule=None, stats_ring=4096):
         from ..parallel import gpu_ps_optim
 
-        if kind not in self.KINDS:
+        if kind not in self.KINDS and not (kind == "sgd" and schedule is not None):
             raise ValueError("the fused step's optimizers are momentum and adam, got %r" % (kind,))
         self.kind = kind
-        self.code = self.KINDS[kind]
-        self.hyper = gpu_ps_optim.hyper_args(kind, momentum, beta1, beta2, epsilon)
+        self.code = self.KINDS.get(kind, 0)
+        self.hyper = gpu_ps_optim.hyper_args(kind, momentum, beta1, beta2, epsilon) or (0.0,) * 3
         self.slots = [torch.zeros(NPARAM, device=device, dtype=torch.float32)
                       for _ in range(gpu_ps_optim.num_slots(kind))]
-        self.tp = torch.zeros(2, device=device, dtype=torch.int32)
+        self.schedule = schedule
+        self.block = self.rates = None
+        if schedule is None:
+            self.tp = torch.zeros(2, device=device, dtype=torch.int32)
+        else:
+            self.block = torch.from_numpy(schedule.block_words()).to(device)
+            if self.block.data_ptr() % 32:
+                raise ValueError("the schedule block must be 32-byte aligned")
+            self.tp = self.block[:2]
+            self.rates = torch.zeros(int(stats_ring), device=device, dtype=torch.float32)
         _check_flat(*self.slots)
 
     def set_step(self, s):
@@ -202,7 +219,12 @@ class PipelinedOpt:
     def args(self):
         """(kind, s0, s1, tp, h0, h1, h2) as the launchers take them."""
         s = self.slots
-        return (self.code, ptr(s[0]), ptr(s[1]) if len(s) > 1 else 0, ptr(self.tp)) + self.hyper
+        return (self.code, ptr(s[0]) if s else 0, ptr(s[1]) if len(s) > 1 else 0,
+                ptr(self.tp)) + self.hyper
+
+    def sched_args(self, stats=True):
+        """``args()`` and the rate ring, as the scheduled launchers take them."""
+        return self.args() + (ptr(self.rates) if stats else 0,)
 
 
 def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, par,
@@ -218,9 +240,16 @@ def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, a
     if p_old.data_ptr() == p_new.data_ptr():
         raise ValueError("the pipelined step needs distinct ping-pong buffers")
     h, s = hip(), stream_handle()
-    h.mlp_lean_fwdapply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x), ptr(x),
-                            ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
-                            ws.stats_ring, ws.B, 1 if apply else 0, int(par), *opt.args(), s)
+    if opt.schedule is not None:  # lr: the base rate; the kernel computes the applied step's
+        _check_sched(opt, ws)
+        h.mlp_lean_fwdapply_sched(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
+                                  ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
+                                  ws.stats_ring, ws.B, 1 if apply else 0, int(par),
+                                  *opt.sched_args(stats), s)
+    else:
+        h.mlp_lean_fwdapply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
+                                ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
+                                ws.stats_ring, ws.B, 1 if apply else 0, int(par), *opt.args(), s)
     h.mlp_lean_head(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s)
 
 
@@ -229,9 +258,33 @@ def flush_pipelined_opt(p_old, p_new, x_prev, ws: StepWorkspace, lr, par, opt: P
     """``flush_pipelined`` with momentum / Adam (the apply-only instantiation)."""
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
+    if opt.schedule is not None:
+        _check_sched(opt, ws)
+        hip().mlp_apply_sched(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev), ptr(ws.buf),
+                              ptr(ws.ctr), ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B,
+                              int(par), *opt.sched_args(stats), stream_handle())
+        return
     hip().mlp_apply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev), ptr(ws.buf), ptr(ws.ctr),
                         ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, int(par),
                         *opt.args(), stream_handle())
+
+
+def _check_sched(opt, ws):
+    """The rate ring is indexed like the stats ring: same length."""
+    if opt.rates.numel() != ws.stats_ring:
+        raise ValueError("the rate ring must have the stats ring's length (%d), got %d"
+                         % (ws.stats_ring, opt.rates.numel()))
+
+
+def scheduled_rate(ws: StepWorkspace, opt: PipelinedOpt, lr, out, publish=True):
+    """One wave (``mlp_lr_sched``): the scheduled rate of step ``ctr - 1`` -- the step whose
+    gradient is pending in the all-reduce engine, which has already advanced the counter -- into
+    ``out`` (f32 [1], ``ops.optim``'s ``lr_tensor``) and, with ``publish``, into the rate ring.
+    Graph-capturable: nothing is baked."""
+    _check_sched(opt, ws)
+    hip().mlp_lr_sched(ptr(ws.ctr), ptr(opt.block), float(lr), ptr(out),
+                       ptr(opt.rates) if publish else 0, ws.stats_ring, stream_handle())
+    return out
 
 
 def step_xgmi(p, x, labels, ws: StepWorkspace, lr, comm, stats=True):

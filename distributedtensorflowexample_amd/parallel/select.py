@@ -137,7 +137,7 @@ def pick_small_allreduce(rccl, mode, world, rank, dev, iters=200, n=None, xgmi_k
 
 def pick_mlp_engine(params, x, y, batch_size, lr, ar_comm, world, rank, dev, mode="auto",
                     xgmi_key="dtfx/xgmi/fused", verify_steps=20, time_steps=400, x_all=None,
-                    timeout_s=2.0):
+                    timeout_s=2.0, optimizer="sgd", lr_schedule=None):
     """Data-parallel engine of the fused MLP trainer, one of
       ``("allreduce", ar_comm)`` -- flat gradient, separate all-reduce launch, deferred apply;
       ``("fused", XgmiComm)``   -- gradient exchange inside the weight-gradient kernel;
@@ -157,6 +157,8 @@ def pick_mlp_engine(params, x, y, batch_size, lr, ar_comm, world, rank, dev, mod
     ``verify_steps`` identical SGD steps, keep the replicas bit-identical, and (mode "auto") be
     the fastest over ``time_steps`` graph-replayed steps (max over ranks); mode "fused" /
     "factor" forces that engine once verified.  Every rank takes the same decision.
+    The exchange engines apply gradient descent at a constant rate: with an ``optimizer`` other
+    than sgd or an ``lr_schedule`` the all-reduce engine it is, whatever ``mode`` says.
     Returns (kind, comm, {engine: us_per_step} or None)."""
     from ..train.fused_mlp import FusedMLPTrainer
 
@@ -165,7 +167,10 @@ def pick_mlp_engine(params, x, y, batch_size, lr, ar_comm, world, rank, dev, mod
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         return bool(t.item())
 
-    if world < 2 or world > 8 or mode == "allreduce":
+    from ..ops.lr_schedule import resolve
+
+    if (world < 2 or world > 8 or mode == "allreduce" or optimizer != "sgd"
+            or resolve(lr_schedule) is not None):
         return "allreduce", ar_comm, None
     kinds = {"auto": ["fused", "fused2", "fused2x", "factor", "factor2"], "fused": ["fused"],
              "fused2": ["fused2"], "fused2x": ["fused2x"], "factor": ["factor"],

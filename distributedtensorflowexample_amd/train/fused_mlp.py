@@ -62,6 +62,18 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   parallel: the all-reduce engine applies the reduced gradient with ``ops.optim``'s
   ``scale_`` + ``momentum_`` / ``adam_`` in place (``t`` from the device counter) before the
   next step's launches.
+* ``lr_schedule`` (an ``ops.lr_schedule.LRSchedule``; ``--lr_schedule``): the rate of every
+  step is computed ON THE DEVICE from the step word the optimizer variants already read, by
+  scheduled instantiations of the first launch (``mlp_lean_fwdapply_sched``; scheduled sgd is
+  one of them, with the step pair and no slot plane).  ``learning_rate`` is the base rate;
+  nothing is baked into a captured graph or a C++ host loop, and ``seek`` puts a resumed run
+  back on the curve.  The stats lane publishes each step's rate to an f32 ring parallel to the
+  stats ring (``learning_rate()`` / ``learning_rates()``).  ``None`` or the constant kind
+  without warm-up is today's trainer and launches exactly today's kernels.  The all-reduce
+  engine computes the pending step's rate with a one-wave kernel into a device float that
+  ``ops.optim`` reads (``lr_tensor``), sgd included (in place, not the deferred apply).  The
+  exchange engines, the persistent launch, the three-launch direct step, ``DTFX_MLP_KS=14``
+  and the fused flush refuse a schedule.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -75,6 +87,7 @@ import time
 
 import torch
 
+from ..ops import lr_schedule as lr_schedule_mod
 from ..ops import mlp_step, optim
 from ..ops._ext import stream_handle
 from ..parallel import gpu_ps_optim
@@ -85,7 +98,22 @@ class FusedMLPTrainer:
                  world_size=1, stats_ring=4096, global_step=0, max_graph_steps=1024,
                  fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
-                 beta2=0.999, epsilon=1e-8):
+                 beta2=0.999, epsilon=1e-8, lr_schedule=None):
+        # --lr_schedule: refused first where the rate is a by-value argument of every launch
+        self.sched = lr_schedule_mod.resolve(lr_schedule)
+        if self.sched is not None:
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("lr_schedule: the exchange engines (fused_comm / factor_comm) "
+                                 "train at a constant rate; use the all-reduce engine")
+            if not pipeline and allreduce is None and int(world_size) == 1:
+                raise ValueError("lr_schedule: the three-launch direct step (pipeline=False) "
+                                 "trains at a constant rate")
+            if params.is_cuda and allreduce is None and int(world_size) == 1:
+                from ..ops._ext import hip
+
+                if hip().mlp_single_ks() != 28:
+                    raise ValueError("lr_schedule: DTFX_MLP_KS=14 has no learning-rate schedule "
+                                     "variant")
         # --optimizer momentum | adam: refused first where only gradient descent exists
         self.optimizer = gpu_ps_optim.check_kind(optimizer)
         if self.optimizer != "sgd":
@@ -146,11 +174,16 @@ class FusedMLPTrainer:
             or fused_comm is not None
             or (factor_comm is not None and self.B <= 128)))
         # --optimizer momentum | adam (module docstring): slot planes owned by the trainer
+        # lr_schedule: the same object also carries the schedule block and the rate ring, and
+        # exists for scheduled sgd too (no slot plane) -- the scheduled step is an OptArgs one
         self.opt = None
-        if self.optimizer != "sgd":
+        if self.optimizer != "sgd" or self.sched is not None:
             self.opt = mlp_step.PipelinedOpt(self.optimizer, self.device, momentum, beta1, beta2,
-                                             epsilon)
+                                             epsilon, schedule=self.sched, stats_ring=stats_ring)
             self.opt.set_step(global_step)
+        # the all-reduce engine's scheduled rate (ops.optim's lr_tensor)
+        self._lr_dev = (torch.zeros(1, device=self.device, dtype=torch.float32)
+                        if self.sched is not None else None)
         self.max_graph_steps = int(max_graph_steps)
         self._graphs = {}
         self._pool = None
@@ -220,17 +253,25 @@ class FusedMLPTrainer:
         current buffer (``ops.optim``), so the parity never moves."""
         return self.opt is not None and not self.pipelined
 
-    def _apply_reduced(self, p, slots):
+    def _apply_reduced(self, p, slots, publish=True):
         """The pending all-reduced gradient through the optimizer, in place on ``p`` /
         ``slots`` (graph-capturable: Adam's t is the device counter, which the step that
-        produced the gradient already advanced to its ``global_step + 1``)."""
+        produced the gradient already advanced to its ``global_step + 1``).  With a schedule
+        the pending step's rate -- step ``counter - 1`` -- is computed on the device first and
+        read by the optimizer kernel (``publish``: also written to the rate ring)."""
         optim.scale_(self.grad, 1.0 / self.world_size)
         h = self.opt.hyper
-        if self.optimizer == "momentum":
-            optim.momentum_(p, self.grad, slots[0], self.lr, momentum=h[0])
+        lrt = None
+        if self.sched is not None:
+            lrt = mlp_step.scheduled_rate(self.ws, self.opt, self.lr, self._lr_dev, publish)
+        if self.optimizer == "sgd":
+            optim.sgd_(p, self.grad, self.lr, lr_tensor=lrt)
+        elif self.optimizer == "momentum":
+            optim.momentum_(p, self.grad, slots[0], self.lr, momentum=h[0], lr_tensor=lrt)
         else:
             optim.adam_(p, self.grad, slots[0], slots[1], self.lr, 0, beta1=h[0], beta2=h[1],
-                        eps=h[2], weight_decay=0.0, adamw=False, step_tensor=self.ws.ctr)
+                        eps=h[2], weight_decay=0.0, adamw=False, step_tensor=self.ws.ctr,
+                        lr_tensor=lrt)
 
     def flush(self):
         """Apply the pending update in place (DP: p -= lr/N * grad; pipelined: the last
@@ -279,7 +320,7 @@ class FusedMLPTrainer:
             if self.pending and self._inplace:
                 out, sl = self.bufs[self.cur].clone(), [t.clone() for t in self.opt.slots]
                 g = self.grad.clone()  # (_apply_reduced scales the gradient in place)
-                self._apply_reduced(out, sl)
+                self._apply_reduced(out, sl, publish=False)  # (the rate ring does not move)
                 self.grad.copy_(g)
                 return out, sl
             out = self.snapshot()  # (pipelined on one GPU: flushed; slots then current)
@@ -508,10 +549,11 @@ class FusedMLPTrainer:
 
             ws = self.ws
             if self.opt is not None:  # the optimizer form of the plan (slot pointers bound too)
+                oargs = self.opt.args() if self.sched is None else self.opt.sched_args()
                 plan = hip().MlpRunOptPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
                                            ptr(self.labels), self.nbatches, ptr(ws.buf),
                                            ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, self.B,
-                                           *self.opt.args())
+                                           *oargs)
                 a = self._host_args = (plan.run, self.device.index, None)
             elif os.environ.get("DTFX_MLP_PLAN", "1") != "0":
                 # the buffers bound once in a C++ plan: the call before the first kernel
@@ -602,6 +644,9 @@ class FusedMLPTrainer:
         from ..ops._ext import hip, ptr, stream_handle
 
         steps = int(steps)
+        if self.sched is not None:
+            raise ValueError("run_persistent: the persistent launch trains at a constant rate "
+                             "(lr_schedule is not supported)")
         if not self.persistent_ok:
             raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
                                "(shuffle off, optimizer sgd)")
@@ -705,6 +750,32 @@ class FusedMLPTrainer:
             start = end - ring
         idx = torch.arange(start, end) % ring
         return self.ws.stats[idx.to(self.device)].cpu()
+
+    def _rates(self):
+        """The rate ring, every step run so far recorded (a step's rate is written by the
+        launch that applies it: a pending update is applied first, as ``stats()`` does)."""
+        if self.sched is None:
+            raise RuntimeError("learning_rate(): the trainer has no lr_schedule (the rate is "
+                               "the constant learning_rate)")
+        self._verified()
+        if self.pending and (self.pipelined or self._inplace):
+            self.flush()
+        return self.opt.rates
+
+    def learning_rate(self, step=None):
+        """The rate the kernel applied for ``step`` (default: the last step), as f32."""
+        r = self._rates()
+        s = (self.global_step() - 1) if step is None else int(step)
+        return float(r[s % self.ws.stats_ring].item())
+
+    def learning_rates(self, start, end):
+        """The applied rates of steps [start, end) as a CPU f32 tensor [n]."""
+        r = self._rates()
+        ring = self.ws.stats_ring
+        if end - start > ring:
+            start = end - ring
+        idx = torch.arange(start, end) % ring
+        return r[idx.to(self.device)].cpu()
 
 
 def benchmark_steps(trainer, steps, warmup, barrier=None, use_graph=True):

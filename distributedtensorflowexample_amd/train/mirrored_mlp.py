@@ -20,7 +20,7 @@ import torch
 import torch.distributed as dist
 
 from ..models import mlp as mlp_model
-from ..ops import mlp_step, nn, optim
+from ..ops import lr_schedule, mlp_step, nn, optim
 from ..ops.shuffle import shuffle_index
 from ..parallel import gpu_ps_optim
 from ..parallel.comm import NativeComm, TorchComm
@@ -66,6 +66,12 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     if opt_kind != "sgd" and getattr(flags, "zero1", False):
         raise ValueError("--optimizer %s does not support --zero1: the sharded update applies "
                          "gradient descent only" % opt_kind)
+    # --lr_schedule: on the device in the fused step / the all-reduce engine (train/fused_mlp.py),
+    # LRSchedule.value_f32 per step on the autograd path; a pure function of global_step, so a
+    # restored run continues on the curve and checkpoints hold nothing new
+    sched = lr_schedule.from_flags(flags)
+    if sched is not None and getattr(flags, "zero1", False):
+        lr_schedule.refuse(flags, "--zero1 (the sharded update)")
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -121,10 +127,10 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         fused = factor = x_all = None
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
-                and opt_kind == "sgd"):
+                and opt_kind == "sgd" and sched is None):
             # exchange engine (fused into the backward kernel / factor all-gather) when
-            # verified and faster than the all-reduce engine (sgd only: with an optimizer the
-            # all-reduce engine it is)
+            # verified and faster than the all-reduce engine (sgd at a constant rate only: with
+            # an optimizer or a schedule the all-reduce engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -146,7 +152,7 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              x_all=x_all if factor is not None else None, rank=rank,
                              pipeline=pipe if comm is not None else True,
                              shuffle=shuffle, shuffle_seed=shuffle_seed, optimizer=opt_kind,
-                             **opt_kw)
+                             lr_schedule=sched, **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -194,17 +200,21 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                 g = ddp.flat_grad[:model.flat.numel()]
             else:
                 g = model.flat.grad
+            # the rate of step i = global_step (the device arithmetic, emulated in f32)
+            lr = (flags.learning_rate if sched is None
+                  else float(sched.value_f32(flags.learning_rate, i)))
+            state["rates"].append(lr)
             with torch.no_grad():
                 if opt_kind == "momentum":
-                    optim.momentum_(model.flat.data, g, cpu_slots[0], flags.learning_rate,
+                    optim.momentum_(model.flat.data, g, cpu_slots[0], lr,
                                     momentum=opt_kw["momentum"])
                 elif opt_kind == "adam":  # t = global_step + 1 of this step
                     optim.adam_(model.flat.data, g, cpu_slots[0], cpu_slots[1],
-                                flags.learning_rate, i + 1, beta1=opt_kw["beta1"],
+                                lr, i + 1, beta1=opt_kw["beta1"],
                                 beta2=opt_kw["beta2"], eps=opt_kw["epsilon"], weight_decay=0.0,
                                 adamw=False)
                 else:
-                    optim.sgd_(model.flat.data, g, flags.learning_rate)
+                    optim.sgd_(model.flat.data, g, lr)
             return float(loss), float(acc)
 
     # one name tuple per slot plane, kernels in TF layout like the variables themselves
@@ -319,13 +329,19 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             if use_gpu:
                 tr.run(n)
                 stats = tr.stats_range(s0, s0 + n)
+                rates = tr.learning_rates(s0, s0 + n).tolist() if sched is not None else None
             else:
+                state["rates"] = []
                 stats = torch.tensor([step_fn() for _ in range(n)])
+                rates = state["rates"] if sched is not None else None
             step = global_step()
             state["step"] = step
             maybe_inject_fault(rank, step)
             if writer is not None:
                 writer.add_scalar_series(["loss", "accuracy"], range(s0, s0 + n), stats.tolist())
+                if rates is not None:  # the rate each step applied
+                    writer.add_scalar_series(["learning_rate"], range(s0, s0 + n),
+                                             [[r] for r in rates])
             cost = float(stats[-1, 0])
             history.append((step, cost, float(stats[-1, 1])))
             if is_chief and step % chunk == 0:

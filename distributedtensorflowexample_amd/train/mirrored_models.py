@@ -38,6 +38,9 @@ def _dist_env():
 def train_model_mirrored(flags, log=print):
     rank, world, local = _dist_env()
     use_gpu = torch.cuda.is_available() and flags.device != "cpu"
+    from ..ops import lr_schedule
+
+    lr_schedule.refuse(flags, "--model %s" % flags.model)  # (before any process group / device)
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))

@@ -137,6 +137,10 @@ class Worker:
         self.optimizer = gpu_ps_optim.validate(getattr(flags, "optimizer", "sgd"),
                                                getattr(flags, "ps_device", "cpu"),
                                                bool(getattr(flags, "use_locking", False)))
+        # --lr_schedule: the parameter store's apply kernels take one constant rate
+        from ..ops import lr_schedule
+
+        lr_schedule.refuse(flags, "--strategy ps_async (--ps_device cpu and gpu)")
         if device is None or device == "auto":
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)

@@ -67,6 +67,21 @@ def main(argv=None):
         if getattr(FLAGS, "zero1", False):
             raise SystemExit("--optimizer %s does not support --zero1: the sharded update "
                              "applies gradient descent only" % FLAGS.optimizer)
+    # --lr_schedule: validated here; only the mirrored MLP paths evaluate one (the ps of a
+    # ps_async cluster included: no task of it starts with a schedule it would ignore)
+    from distributedtensorflowexample_amd.ops import lr_schedule
+
+    try:
+        if FLAGS.strategy != "mirrored":
+            lr_schedule.refuse(FLAGS, "--strategy ps_async (--ps_device cpu and gpu)")
+        elif FLAGS.model != "mlp":
+            lr_schedule.refuse(FLAGS, "--model %s" % FLAGS.model)
+        elif getattr(FLAGS, "zero1", False):
+            lr_schedule.refuse(FLAGS, "--zero1 (the sharded update)")
+        else:
+            lr_schedule.from_flags(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if FLAGS.strategy == "mirrored" and FLAGS.model != "mlp":
         from distributedtensorflowexample_amd.train.mirrored_mlp import shutdown_mirrored
         from distributedtensorflowexample_amd.train.mirrored_models import train_model_mirrored
