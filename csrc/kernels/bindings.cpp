@@ -13,62 +13,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "mlp_step_api.h"
+
 namespace py = pybind11;
 
 namespace dtfx {
-void mlp_fwd_launch(const float*, const float*, float, float*, const float*, float*, int,
-                    hipStream_t, unsigned long long*);
-void mlp_head_launch(const float*, const float*, float, float*, const int*, float*, int,
-                     hipStream_t, unsigned long long*);
-void mlp_wgrad_launch(float*, float, float*, const float*, float*, int*, float*, int, int,
-                      hipStream_t, unsigned long long*);
-long long mlp_workspace_floats(int);
-void mlp_ps_stage(const float*, const int*, float*, int*, int, hipStream_t);
-void mlp_ps_worker_step(float*, const float*, float*, const float*, const int*, float*, int*,
-                        float*, float*, int*, float*, int, const float*, int, float*, float*,
-                        hipStream_t);
-void mlp_tf_layout_launch(const float*, float*, int, const float*, int, hipStream_t);
-void mlp_fwdapply_launch(const float*, float*, float, const float*, const float*, float*, int*,
-                         float*, int, int, int, hipStream_t, int);
-void mlp_head2_launch(const float*, const int*, float*, int, hipStream_t, int);
-void mlp_head2_single_launch(const float*, const int*, float*, int, hipStream_t);
-void mlp_rowmajor_layout(int, long long*);
-void wave_reduce_scatter_test_launch(const float*, float*, int, hipStream_t);
-int mlp_single_ks_query();
-int mlp_set_flush_fused(int on);
-void mlp_pipelined_trace_launch(const float*, float*, float, const float*, const float*,
-                                const int*, float*, int*, float*, int, int, hipStream_t,
-                                unsigned long long*, unsigned long long*, unsigned long long*);
-void mlp_lean_fwdapply_launch(const float*, float*, float, const float*, const float*, float*, int*,
-                              float*, int, int, int, hipStream_t);
-void mlp_lean_head_launch(const float*, const int*, float*, int, hipStream_t);
-void mlp_run_pipelined_launch(float*, float*, int, int, float, const float*, const int*, int, int,
-                              int, float*, int*, float*, int, int, hipStream_t, int);
-void mlp_apply_launch(const float*, float*, float, const float*, float*, int*, float*, int, int,
-                      hipStream_t);
-// momentum / adam variants of the lean two-launch step (mlp_step.hip)
-struct MlpOpt {
-  int kind;
-  float *s0, *s1;
-  int* tp;
-  float h0, h1, h2;
-  int sched = 0;          // != 0: the scheduled instantiations (tp heads the 8-word schedule block)
-  float* lrs = nullptr;   // their rate ring
-};
-void mlp_lr_sched_launch(const int*, const int*, float, float*, float*, int, hipStream_t);
-void mlp_lean_fwdapply_opt_launch(const float*, float*, float, const float*, const float*, float*,
-                                  int*, float*, int, int, int, int, const MlpOpt&, hipStream_t);
-void mlp_apply_opt_launch(const float*, float*, float, const float*, float*, int*, float*, int,
-                          int, int, const MlpOpt&, hipStream_t);
-void mlp_run_pipelined_opt_launch(float*, float*, int, int, float, const float*, const int*, int,
-                                  int, int, float*, int*, float*, int, int, hipStream_t, int,
-                                  const MlpOpt&);
-long long mlp_persistent_ll_words();
-int mlp_persistent_blocks();
-int mlp_persistent_trace_steps();
-void mlp_persistent_launch(float*, const float*, const int*, int, int, int, float, unsigned,
-                           unsigned long long*, int*, float*, int, int, long long,
-                           unsigned long long*, hipStream_t);
 void calib_launch(int, int, int, const int*, const float*, float*, hipStream_t);
 void clock_probe_launch(int, int, unsigned long long*, float*, hipStream_t);
 void gemm_f32_launch(bool, bool, int, int, int, float, const float*, int, const float*, int,
@@ -89,10 +38,6 @@ void act_bwd_launch(long long, int, const float*, const float*, float*, hipStrea
 void act_fwd_launch(long long, int, const float*, float*, hipStream_t);
 void shuffle_rows_launch(float*, const float*, int*, const int*, long long, int, long long,
                          long long, unsigned, unsigned, hipStream_t);
-void mlp_eval_launch(const float*, const float*, const int*, int, void*, int*, float*, hipStream_t);
-int mlp_eval_acc_bytes();
-int mlp_eval_row_tile();
-int mlp_eval_max_rows();
 }  // namespace dtfx
 
 void register_rccl(py::module_& m);
@@ -247,12 +192,13 @@ PYBIND11_MODULE(_hip, m) {
     float* stats;
     int ring, B;
   };
+  static const auto bound = [](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
+                               uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B) {
+    return MlpRunPlan{P<float>(p0), P<float>(p1), P<const float>(x), P<const int>(lab),
+                      nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B};
+  };
   py::class_<MlpRunPlan>(m, "MlpRunPlan")
-      .def(py::init([](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
-                       uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B) {
-        return MlpRunPlan{P<float>(p0), P<float>(p1), P<const float>(x), P<const int>(lab),
-                          nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B};
-      }))
+      .def(py::init(bound))
       .def("run", [](const MlpRunPlan& p, int cur, int pending, float lr, int pos, int n,
                      int flush, uintptr_t s) {
         py::gil_scoped_release nogil;
@@ -323,23 +269,14 @@ PYBIND11_MODULE(_hip, m) {
                               P<float>(lrs), ring, S(s));
   }, "one wave: the scheduled rate of step ctr - 1 into out[0] (ops.optim's lr_tensor) and, with "
      "lrs != 0, into the rate ring");
-  struct MlpRunOptPlan {
-    float *p0, *p1;
-    const float* x;
-    const int* labels;
-    int nbatches;
-    float* ws;
-    int* ctr;
-    float* stats;
-    int ring, B;
+  struct MlpRunOptPlan : MlpRunPlan {  // the same bound buffers, and the optimizer's
     dtfx::MlpOpt opt;
   };
   py::class_<MlpRunOptPlan>(m, "MlpRunOptPlan")
       .def(py::init([](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
                        uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int kind,
                        uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1, float h2) {
-        return MlpRunOptPlan{P<float>(p0), P<float>(p1), P<const float>(x), P<const int>(lab),
-                             nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B,
+        return MlpRunOptPlan{bound(p0, p1, x, lab, nbatches, ws, ctr, stats, ring, B),
                              dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1,
                                           h2}};
       }))
@@ -347,8 +284,7 @@ PYBIND11_MODULE(_hip, m) {
                        uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int kind,
                        uintptr_t s0, uintptr_t s1, uintptr_t blk, float h0, float h1, float h2,
                        uintptr_t lrs) {  // the scheduled form (mlp_lean_fwdapply_sched)
-        return MlpRunOptPlan{P<float>(p0), P<float>(p1), P<const float>(x), P<const int>(lab),
-                             nbatches, P<float>(ws), P<int>(ctr), P<float>(stats), ring, B,
+        return MlpRunOptPlan{bound(p0, p1, x, lab, nbatches, ws, ctr, stats, ring, B),
                              dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(blk), h0, h1,
                                           h2, 1, P<float>(lrs)}};
       }))

@@ -7,8 +7,8 @@
 //
 // h and the logits never reach global memory; every element of x is loaded exactly once, by
 // one lane.  All matrix work is v_mfma_f32_16x16x4_f32 (exact f32; lane layout and the
-// float4-feeds-4-MFMAs K permutation as in mlp_step.hip).  Parameter layout: the flat
-// 79,510-element buffer of mlp_step.hip.
+// float4-feeds-4-MFMAs K permutation as in mlp_step_ws.h).  Parameter layout: the flat
+// 79,510-element buffer of mlp_model.h.
 //
 // Decomposition.  The arithmetic first: n = 10,000 rows x 784 x 112 (hidden width padded to 7
 // tiles of 16) x 2 = 1.76 GFLOP of f32 MFMA, 11.2 us at the 157 TF peak if all 1024 SIMDs had
@@ -68,6 +68,8 @@
 // nothing.  labels == nullptr: predict only, the accumulator is neither zeroed nor written.
 // Tail rows (any n >= 1) load row n - 1 instead and are never stored or counted.
 #include "common.h"
+#include "mlp_model.h"
+#include "mlp_step_api.h"
 
 #include <cmath>
 #include <stdexcept>
@@ -76,9 +78,7 @@
 namespace dtfx {
 namespace mlpeval {
 
-constexpr int D = 784, H = 100, C = 10;
-constexpr int HT = 7;                 // hidden tiles of 16 (112 padded)
-constexpr int OFF_W1 = 0, OFF_B1 = H * D, OFF_W2 = OFF_B1 + H, OFF_B2 = OFF_W2 + C * H;
+using namespace mlp_model;  // D, H, C, HT, OFF_*: the one definition (mlp_model.h)
 constexpr int NW = 4;                 // waves per workgroup
 constexpr int T = NW * 16;            // rows per workgroup
 constexpr int KC = 112;               // features per staged W1 chunk

@@ -44,6 +44,8 @@
 // rounding (the compiler may contract a different product of a short dot into an FMA;
 // tests/test_kernels_gpu.py::test_persistent_trainer_*).
 #include "common.h"
+#include "mlp_model.h"
+#include "mlp_step_api.h"
 
 #include <stdexcept>
 
@@ -52,14 +54,13 @@ namespace mlpp {
 
 using u64 = unsigned long long;
 
-constexpr int D = 784, H = 100, C = 10;
-constexpr int HT = 7;             // hidden tiles of 16 (112 padded)
+// sizes and the flat parameter layout: the one definition (mlp_model.h; not its MAXB)
+using mlp_model::D, mlp_model::H, mlp_model::C, mlp_model::HT, mlp_model::NPARAM;
+using mlp_model::OFF_W1, mlp_model::OFF_B1, mlp_model::OFF_W2, mlp_model::OFF_B2;
 constexpr int KS = 14, KW = 56;   // feature slices of a hidden tile (3.5 MFMA groups of 16)
 constexpr int NW1 = HT * KS;      // 98 W1 blocks
 constexpr int NBLK = NW1 + HT;    // + 7 small-parameter blocks = 105
-constexpr int MAXB = 128;
-constexpr int OFF_W1 = 0, OFF_B1 = H * D, OFF_W2 = OFF_B1 + H, OFF_B2 = OFF_W2 + C * H;
-constexpr int NPARAM = OFF_B2 + C;
+constexpr int MAXB = 128;         // this engine's own bound: the LL layout below is sized by it
 
 // granule buffer layout (u64 words)
 constexpr int SLAB_ROW = 128;                                 // words per (ks, row): j < 100
@@ -82,7 +83,6 @@ constexpr long long OFF_ERR = OFF_SP + 2 * SP_PAR;
 constexpr long long LL_WORDS = OFF_ERR + 32;
 constexpr int TRACE_STEPS = 64;
 
-static_assert(NPARAM == 79510, "parameter count of worker.py:50-53");
 static_assert(KS * KW == D && HDL + 16 <= HST && HST + 2 <= HEAD_ROW, "layout");
 
 struct Args {

@@ -1,0 +1,131 @@
+// Fused MLP step (mlp_step.hip): stateful optimizers and learning-rate schedules inside the lean
+// two-launch step's first launch.
+//
+// Momentum and Adam live in that first launch too (mlp_lean_fwdapply_opt_kernel, OptArgs below):
+// the lane that owns a parameter element also owns its slot values, so no gradient buffer and no
+// optimizer launch exist; the SGD instantiations are unchanged (profiles/fused_optim/).
+// Learning-rate schedules (sched_rate, mlp_lean_fwdapply_sched_kernel): scheduled instantiations
+// of that entry point -- sgd among them -- compute the rate of the step they apply from the step
+// word and an 8-word schedule block, once per wave, and the stats lane publishes it to a rate
+// ring; the constant-rate kernels are unchanged (profiles/lr_schedule/: +0.03 .. +0.2 us a step).
+#pragma once
+#include "mlp_step_ws.h"
+
+namespace dtfx {
+namespace mlp {
+
+// ---------------------------------------------------------------------------
+// Stateful optimizers inside the lean two-launch step (mlp_lean_fwdapply_opt_kernel): gpu_ps.hip's
+// formulas (ops/optim.py's momentum_ / adam_, no weight decay, no Nesterov) applied by the lane
+// that owns the element -- the A16 item of fwdapply_block for W1, the ok[i] lane of wgrad_small
+// for b1 / W2 / b2.  The slot planes s0 (momentum: accum; adam: m) and s1 (adam: v) are flat f32
+// [NPARAM] buffers in the parameter layout, updated IN PLACE (one owner per element, read once
+// and written once by it); only the parameters ping-pong.
+//   momentum  accum = mu * accum + g;  p -= lr * accum   (mu = 0: accum = g and the SGD bits)
+//   adam      m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * g * g
+//             p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// t = global_step + 1 of the step being applied.  It is NOT read from ctr: the stats lane of the
+// small-parameter block jt == 0 writes ctr in this same launch.  tp is a pair of step words
+// indexed by the launch's buffer parity par (the index of p_old in the trainer's ping-pong pair):
+// every wave reads tp[par], the stats lane alone writes tp[par ^ 1] = tp[par] + stats_on, which
+// the NEXT launch (parity par ^ 1) reads -- no word is read and written in one launch.
+// apply == 0 (nothing pending): p_old is copied, no slot byte is written.
+enum : int { OPT_SGD = 0, OPT_MOMENTUM = 1, OPT_ADAM = 2 };
+struct OptArgs {
+  float* s0;
+  float* s1;
+  int* tp;
+  float h0, h1, h2;  // momentum: mu; adam: beta1, beta2, epsilon
+  int apply, par;
+  float* lrs;        // SCHED: the rate ring (f32 [stats_ring], parallel to the stats ring), or null
+};
+// Learning-rate schedules evaluated on the device (the SCHED instantiations; ops/lr_schedule.py
+// is the definition, its value_f32 this arithmetic operation for operation).  The step pair is
+// then the head of an 8-word block [tp0, tp1, kind | staircase << 2, decay_steps, a, inv_decay,
+// inv_warmup, 0], 32-byte aligned.  a = f32(log2 decay_rate) (exponential) or decay_rate (inverse
+// time); inv_warmup = 0 skips the warm-up.  s: the 0-based global_step of the step applied.
+// Wave-uniform: the whole block is fetched at once (sched_load: every word unconditionally, so
+// the wave makes ONE round trip instead of one per word a branch happens to need) and a handful
+// of scalar-side operations follow, every alternative computed and selected.
+//   staircase q: integer division of the step word (float(s) * f32(1 / 3) misses exact multiples)
+//   exponential: exp2(q * log2 rate) on the transcendental unit, as opt_coef's b^t
+enum : int { SCHED_CONSTANT = 0, SCHED_EXPONENTIAL = 1, SCHED_INVERSE_TIME = 2 };
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+struct SchedBlock {
+  i32x4 lo, hi;  // lo = {tp0, tp1, flags, decay_steps}, hi = {a, inv_decay, inv_warmup, 0}
+};
+__device__ __forceinline__ SchedBlock sched_load(const int* __restrict__ blk) {
+  return {*reinterpret_cast<const i32x4*>(blk), *reinterpret_cast<const i32x4*>(blk + 4)};
+}
+__device__ __forceinline__ float sched_rate(float lr0, int s, const SchedBlock& w) {
+  const int kind = w.lo.z & 3, stair = (w.lo.z >> 2) & 1;
+  const unsigned ds = (unsigned)w.lo.w;
+  const float a = __int_as_float(w.hi.x), inv_ds = __int_as_float(w.hi.y);
+  const float inv_warm = __int_as_float(w.hi.z);
+  const float qi = (float)((unsigned)s / ds), qf = (float)s * inv_ds;
+  const float q = stair ? qi : qf;
+  const float e = __builtin_amdgcn_exp2f(q * a);
+  const float r = __builtin_amdgcn_rcpf(__builtin_fmaf(a, q, 1.f));
+  const float decay = kind == SCHED_EXPONENTIAL ? e : kind == SCHED_INVERSE_TIME ? r : 1.f;
+  const float lr = lr0 * decay;
+  const float warm = fminf(1.f, (float)(s + 1) * inv_warm);
+  return inv_warm > 0.f ? lr * warm : lr;
+}
+// momentum: lr, h0 = mu.  adam: lr = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t)
+struct OptCoef {
+  float lr, h0, h1, h2, rbc2;
+};
+template <int OPT, bool SCHED = false>
+__device__ __forceinline__ OptCoef opt_coef(float lr, const OptArgs& oa) {
+  if constexpr (SCHED) {  // the applied step's rate
+    const SchedBlock w = sched_load(oa.tp);
+    lr = sched_rate(lr, oa.par ? w.lo.y : w.lo.x, w);
+  }
+  OptCoef c = {lr, oa.h0, oa.h1, oa.h2, 1.f};
+  if constexpr (OPT == OPT_ADAM) {  // (wave-uniform: once per wave, not per element)
+    // b^t = exp2(t log2 b) on the transcendental unit: 0 <= b < 1, so the product is <= 0, and
+    // wherever b^t is not negligible against 1 (t |log2 b| < 24) its relative error stays below
+    // 24 ulp of the exponent ~ 3e-6 -- 1e-6 of an update of ~lr.  powf would add ~6 KB of code
+    // per instantiation in front of the apply.
+    const float tf = (float)(oa.tp[oa.par] + 1);
+    c.lr = lr / (1.f - __builtin_amdgcn_exp2f(tf * __builtin_amdgcn_logf(oa.h0)));
+    c.rbc2 = rsqrtf(1.f - __builtin_amdgcn_exp2f(tf * __builtin_amdgcn_logf(oa.h1)));
+  }
+  return c;
+}
+// -> the new parameter value; s0 / s1 become the new slot values
+template <int OPT>
+__device__ __forceinline__ float opt_update(float p, float g, float& s0, float& s1,
+                                            const OptCoef& c) {
+  if constexpr (OPT == OPT_SGD) {  // (scheduled gradient descent: the SGD step's own expression)
+    return p - c.lr * g;
+  } else if constexpr (OPT == OPT_MOMENTUM) {
+    s0 = c.h0 * s0 + g;
+    return p - c.lr * s0;
+  } else {
+    s0 = c.h0 * s0 + (1.f - c.h0) * g;
+    s1 = c.h1 * s1 + (1.f - c.h1) * g * g;
+    // v_sqrt_f32 / v_rcp_f32 (1 ulp each) instead of the correctly rounded sqrtf and division
+    // (~25 instructions per element between the LDS sum and the Wt / p_new stores): 2 ulp of an
+    // update of ~lr, far below half an ulp of p
+    return p - c.lr * s0 * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(s1) * c.rbc2 + c.h2);
+  }
+}
+
+// The all-reduce engine's rate (FusedMLPTrainer._apply_reduced): one wave writes lr(s) of the
+// pending step -- s = ctr - 1: the step that produced the gradient has advanced the counter --
+// into a device float that ops.optim's lr_tensor reads, and into the rate ring (lrs may be null).
+__global__ __launch_bounds__(64) void mlp_lr_sched_kernel(const int* __restrict__ ctr,
+                                                          const int* __restrict__ blk, float lr0,
+                                                          float* __restrict__ out,
+                                                          float* __restrict__ lrs, int ring) {
+  const int s = *ctr - 1;
+  const float rate = sched_rate(lr0, s, sched_load(blk));
+  if (threadIdx.x == 0) {
+    *out = rate;
+    if (lrs && s >= 0) lrs[s % ring] = rate;
+  }
+}
+
+}  // namespace mlp
+}  // namespace dtfx

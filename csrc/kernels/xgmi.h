@@ -54,35 +54,6 @@ constexpr int MLP_XG_EPOCHS = 1024;
 // mlp_fwdapply_kernel<.., XW> use [0, 392) (never on the same communicator)
 constexpr int MLP_XG_SMALL_EPOCH = 400;
 constexpr int MLP_XG_HEAD_EPOCH = 512;
-
-// Factor engine (sufficient-factor exchange): head launch that all-gathers the backprop
-// factors dz1 of every rank into dz1A [world][112][BP], then the weight-gradient launch that
-// forms the global dW1 from them and every rank's (resident) batch x, applying directly.
-void mlp_head_xg_launch(const float* p, const int* labels, float* ws, float* dz1A, int B,
-                        hipStream_t stream, const MlpXg& xg, int world, int nslab = 7);
-// Pipelined factor engine: step t-1's global W1 update (from dz1A and every rank's x_prev)
-// fused with step t's forward (head of step t: mlp_head_xg_launch with nslab = 14).
-void mlp_fwdapply_factor_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
-                                const float* x, long long xstride, const float* dz1A, float* ws,
-                                int* ctr, float* stats, int stats_ring, int B, int stats_on,
-                                hipStream_t stream, const MlpXg& xg, int world);
-void mlp_wgrad_factor_launch(float* p, float lr, const float* x, long long xstride,
-                             const float* dz1A, float* ws, int* ctr, float* stats, int stats_ring,
-                             int B, hipStream_t stream, const MlpXg& xg, int world);
-
-// Pipelined fused engine: step t-1's local W1/W2/b gradient tiles exchanged and applied
-// (p_old -> p_new) in the launch that runs step t's forward; the head is the plain one.
-// two_shot: the W1 tiles' exchange as reduce-scatter + all-gather (xg_exchange2): 2 (W-1)/W
-// words per element per rank instead of W-1 (needs the push layout's result region)
-void mlp_fwdapply_xg_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
-                            const float* x, float* ws, int* ctr, float* stats, int stats_ring,
-                            int B, int stats_on, hipStream_t stream, const MlpXg& xg, int world,
-                            int two_shot = 0, unsigned long long* trace = nullptr);
-
-void mlp_wgrad_xg_launch(float* p, float lr, const float* x, float* ws, int* ctr, float* stats,
-                         int stats_ring, int B, hipStream_t stream, const MlpXg& xg, int world);
-// plain head of the pipelined step (mlp_step.hip); nslab = 28 after the fused engines' launch
-void mlp_head2_launch(const float* p, const int* labels, float* ws, int B, hipStream_t stream,
-                      int nslab);
+// (the launchers that take an MlpXg are declared in mlp_step_api.h)
 
 }  // namespace dtfx

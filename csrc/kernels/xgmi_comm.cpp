@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "mlp_step_api.h"
 #include "xgmi.h"
 
 namespace py = pybind11;

@@ -15,7 +15,7 @@ The schedule is a pure function of ``global_step``: a checkpoint needs nothing n
 resumed with ``seek`` continues on the same curve.
 
 ``LRSchedule.value`` is the float64 definition.  ``value_f32`` is the device arithmetic of
-``csrc/kernels/mlp_step.hip`` (``sched_rate``) in numpy float32, operation for operation: the
+``csrc/kernels/mlp_step_opt.h`` (``sched_rate``) in numpy float32, operation for operation: the
 staircase quotient by integer division, ``float(s) * f32(1 / decay_steps)`` otherwise,
 ``exp2(q * f32(log2 decay_rate))``, ``1 / fma(decay_rate, q, 1)``, ``min(1, float(s + 1) *
 f32(1 / warmup_steps))``.  The device's exp2 and reciprocal come from the transcendental unit

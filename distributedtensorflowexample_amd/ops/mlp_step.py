@@ -1,7 +1,8 @@
 """Fused three-launch training step of the reference MNIST MLP.
 
-Python side of ``csrc/kernels/mlp_step.hip``; see that file for the kernel
-design.  The step the reference runs per worker (worker.py:131-141: pull,
+Python side of ``csrc/kernels/mlp_step.hip``; see that file for the map of its engines
+(``csrc/kernels/mlp_step_*.h``, each opening with its kernel design).  The step the
+reference runs per worker (worker.py:131-141: pull,
 forward, loss, backward, ApplyGradientDescent, global_step += 1) becomes::
 
     mlp_fwd   : partial z1 = x . W1 over 7 K slices (343 single-wave blocks)
@@ -39,7 +40,7 @@ MAX_BATCH = 256
 
 # partial z1 slabs the data-parallel engines' first launch writes (their K slicing)
 XG_SLABS = 28
-# 16-byte LL layout of the fused engines' one-shot split exchange (csrc/kernels/mlp_step.hip,
+# 16-byte LL layout of the fused engines' one-shot split exchange (csrc/kernels/mlp_step_xg.h,
 # xg_exchange16): a communicator for fused2 needs slots of XG_SLOT_WORDS words
 XG_W1_BASE = 79616
 XG_SLOT_WORDS = XG_W1_BASE + 7 * 28 * 2 * 2 * 64 * 2
@@ -173,7 +174,7 @@ def flush_pipelined(p_old, p_new, x_prev, ws: StepWorkspace, lr, stats=True):
 
 
 class PipelinedOpt:
-    """Momentum / Adam state of the two-launch step (``csrc/kernels/mlp_step.hip``, OptArgs):
+    """Momentum / Adam state of the two-launch step (``csrc/kernels/mlp_step_opt.h``, OptArgs):
     ``slots`` -- one (momentum: accum) or two (adam: m, v) flat f32 [79510] planes in the
     parameter layout, updated in place by the lane that owns each element; ``tp`` -- the int32
     [2] step pair (a launch of buffer parity ``par`` reads ``tp[par]`` = global_step of the step

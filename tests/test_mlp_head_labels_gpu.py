@@ -1,4 +1,5 @@
-"""The label path and the packed unit pair of the MLP head (head_row, csrc/kernels/mlp_step.hip).
+"""The label path and the packed unit pair of the MLP head (head_row,
+csrc/kernels/mlp_step_3launch.h).
 
 The head reads its row's label with a per-lane vector load issued ahead of the operand loads
 and sums a lane's two hidden units as one pair.  These tests pin what that must not change:

@@ -1,4 +1,5 @@
-"""The operand addressing of the two lean launches' prologues (csrc/kernels/mlp_step.hip,
+"""The operand addressing of the two lean launches' prologues (head_row<.., SB> in
+csrc/kernels/mlp_step_3launch.h, fwdapply_block in csrc/kernels/mlp_step_fwdapply.h;
 profiles/lean_prologue/): the head's 28 slab loads go through one buffer descriptor (lane offset
 in the vector offset, plane and row in the scalar one).  The same series measured the first
 launch's dz1R / x_prev loads through descriptors with 32-bit offsets (the row clamp

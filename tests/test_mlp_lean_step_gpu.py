@@ -1,6 +1,6 @@
 """The lean entry points of the single-GPU two-launch MLP step (mlp_lean_fwdapply /
-mlp_lean_head, csrc/kernels/mlp_step.hip: packed kernel arguments, workspace regions derived
-from the base pointer, phase A's operands requested first) against the
+mlp_lean_head, csrc/kernels/mlp_step_fwdapply.h: packed kernel arguments, workspace regions
+derived from the base pointer, phase A's operands requested first) against the
 kernels they wrap, ``mlp_fwdapply(ks=28)`` + ``mlp_head2(single=1)``.  No floating-point
 operation or summation order differs, so everything is compared BIT for bit.
 

@@ -1,5 +1,6 @@
 """Row-major backprop factors (dz1R / dlR) of the single-GPU two-launch MLP step and the
-class-per-lane head arithmetic (csrc/kernels/mlp_step.hip, wave_reduce_scatter in common.h).
+class-per-lane head arithmetic (head_row in csrc/kernels/mlp_step_3launch.h,
+wave_reduce_scatter in common.h).
 
 Batches: 1, 15, 16, 17 (one row tile, its edges), 100 (the workload), 112 (the padded batch
 itself), 113 (BP = 128 != HP = 112: a swapped pitch shows only here; the generic NGT = 0

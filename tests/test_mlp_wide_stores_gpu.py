@@ -1,6 +1,6 @@
 """The first launch of the lean single-GPU MLP step with its 16-byte W1 apply (mlp_lean_fwdapply,
-csrc/kernels/mlp_step.hip, fwdapply_block<.., A16>: one float4 of p_old / p_new / Wt per live lane
-on all four waves, the partials exchanged through LDS in another layout) against the untouched
+csrc/kernels/mlp_step_fwdapply.h, fwdapply_block<.., A16>: one float4 of p_old / p_new / Wt per
+live lane on all four waves, the partials exchanged through LDS in another layout) against the untouched
 generic pair ``mlp_fwdapply(ks=28)`` + ``mlp_head2(single=1)``, BIT for bit, at what
 tests/test_mlp_lean_step_gpu.py does not reach (the cases were chosen for the slab-store forms
 measured with it, profiles/wide_wt_stores/, and hold for any form of the launch):
