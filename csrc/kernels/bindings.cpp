@@ -13,32 +13,10 @@
 #include <stdexcept>
 #include <string>
 
+#include "f32_api.h"
 #include "mlp_step_api.h"
 
 namespace py = pybind11;
-
-namespace dtfx {
-void calib_launch(int, int, int, const int*, const float*, float*, hipStream_t);
-void clock_probe_launch(int, int, unsigned long long*, float*, hipStream_t);
-void gemm_f32_launch(bool, bool, int, int, int, float, const float*, int, const float*, int,
-                     float, float*, int, const float*, int, const float*, int, bool, hipStream_t);
-void colsum_launch(int, int, const float*, int, float, float*, hipStream_t);
-void softmax_xent_launch(int, int, const float*, int, const int*, const float*, int, int, float,
-                         float*, float*, int, float*, float*, hipStream_t);
-void sgd_launch(long long, float*, const float*, float, const float*, float, hipStream_t);
-void momentum_launch(long long, float*, const float*, float*, float, const float*, float, float,
-                     bool, hipStream_t);
-void adam_launch(long long, float*, const float*, float*, float*, float, const float*, float,
-                 float, float, float, bool, int, const int*, hipStream_t);
-void scale_launch(long long, float*, float, hipStream_t);
-void counter_add_launch(int*, int, hipStream_t);
-void philox_init_launch(long long, float*, unsigned long long, unsigned long long, int, float,
-                        float, hipStream_t);
-void act_bwd_launch(long long, int, const float*, const float*, float*, hipStream_t);
-void act_fwd_launch(long long, int, const float*, float*, hipStream_t);
-void shuffle_rows_launch(float*, const float*, int*, const int*, long long, int, long long,
-                         long long, unsigned, unsigned, hipStream_t);
-}  // namespace dtfx
 
 void register_rccl(py::module_& m);
 void register_nn(py::module_& m);

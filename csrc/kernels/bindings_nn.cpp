@@ -4,124 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 
-namespace py = pybind11;
+#include "nn_api.h"
 
-namespace dtfx {
-void gemm_bf16_set_cfg(int);
-int gemm_bf16_set_pers(int);
-void attn_bwd_set_variant(int);
-void attn_bwd_set_pf(int);
-void ln_bwd_set_slots(int);
-void xent_set_regs(int);
-void ln_bwd_set_h768(int);
-void attn_set_swizzle(int);
-void attn_fwd_set_variant(int);
-void transpose_bf16_batch_launch(const long long*, int, int, hipStream_t);
-void gemm_bf16_launch(bool, bool, bool, int, int, int, const void*, int, const void*, int, void*,
-                      int, float, float, const float*, int, const void*, void*, int, const void*,
-                      int, int, int, int, long long, long long, long long,
-                      float*, hipStream_t, float*, long long, bool);
-void colsum_bf16_launch(const void*, int, int, int, float*, float, hipStream_t);
-void colsum_set_rows_in_flight(int);
-long long gemm_bf16_ws_floats(bool, bool, int, int, int, int, float);
-long long conv_wgrad_ws_floats(int, int, int, int, int, int, int, int, int);
-long long conv_splitk_ws_floats(int, int, int, int, int, int, int, int, int, int);
-void conv_bf16_launch(int, int, int, int, int, int, int, int, int, int, const void*, const void*, int,
-                      void*, float, const void*, float*, float*, int, hipStream_t, const void*,
-                      const void*, const float*, const float*, float*, long long, int);
-void bn_bwd_apply_launch(long long, int, const void*, const void*, const float*, const float*,
-                         const float*, const float*, const float*, void*, hipStream_t);
-void bn_finalize_launch(int, long long, const float*, const float*, float, float*, float*, float*,
-                        float*, float, hipStream_t);
-void bn_apply_launch(long long, int, const void*, const float*, const float*, const float*,
-                     const float*, const void*, int, void*, hipStream_t);
-void bn_apply_stats_launch(long long, int, const void*, const float*, const float*, float, float*,
-                           float*, float*, float*, float, const float*, const float*, const void*,
-                           int, void*, const float*, const float*, const float*, const float*,
-                           float*, float*, float*, float*, hipStream_t);
-void bn_bwd_launch(long long, int, const void*, const void*, const void*, const float*, const float*,
-                   const float*, int, float*, float*, float*, void*, void*, hipStream_t);
-long long bn_bwd_scratch_rows(long long, int);
-void colpart_reduce_launch(int, int, const float*, const float*, float*, float*, hipStream_t);
-bool stem_conv_applies(int, int, int, int, int, int, int, int);
-int stem_conv_fwd_rows(int, int, int);
-void stem_conv_fwd_launch(int, int, int, const void*, const void*, int, void*, float*, float*,
-                          hipStream_t);
-void stem_conv_wgrad_launch(int, int, int, const void*, const void*, float*, int, float,
-                            hipStream_t, const void*, const float*);
-bool conv3x3_c64_applies(int, int, int, int, int, int, int, int);
-void conv3x3_c64_fwd_launch(int, int, int, const void*, const void*, int, void*, float*, float*,
-                            hipStream_t, const float* = nullptr, void* = nullptr);
-void conv3x3_c64_wgrad_launch(int, int, int, const void*, const void*, float*, int, float,
-                              hipStream_t);
-void conv3x3_c64_dgrad_launch(int, int, int, const void*, const void*, int, void*, const void*,
-                              const void*, const float*, const float*, float*, float*, void*, hipStream_t);
-bool conv3x3_c128_applies(int, int, int, int, int, int, int, int);
-bool conv1x1_applies(int, int, int);
-int conv1x1_rows(int, int, int, int);
-void conv1x1_launch(int, int, int, int, const void*, const void*, int, void*, const void*,
-                    const void*, const void*, const float*, const float*, float*, float*, void*,
-                    hipStream_t);
-bool conv1x1_pro_applies(int, int, int, int);
-void conv1x1_pro_launch(int, int, int, int, const void*, const void*, const float*, void*,
-                        const void*, int, void*, const void*, const void*, const void*,
-                        const float*, const float*, float*, float*, void*, hipStream_t,
-                        int = 0, int = 0);
-void conv1x1_pro_fwdbn_launch(int, int, int, int, const void*, const void*, long long,
-                              const float*, const float*, float, float*, float*, float*, float*,
-                              float, const float*, const float*, const float*, const float*,
-                              const float*, const float*, float*, float*, float*, float*, void*,
-                              const void*, int, void*, float*, float*, hipStream_t);
-void conv1x1_pro_bwdbn_launch(int, int, int, const void*, const void*, long long, const float*,
-                              const float*, const float*, const float*, const float*, void*,
-                              const void*, int, void*, const void*, const void*, const void*,
-                              const float*, const float*, float*, float*, void*, hipStream_t, int,
-                              int);
-void bn_fwd_coef_launch(long long, int, const float*, const float*, float, float*, float*, float*,
-                        float*, float, const float*, const float*, const float*, const float*,
-                        const float*, const float*, float*, float*, float*, float*, float*,
-                        hipStream_t);
-void bn_bwd_coef_launch(long long, int, const float*, const float*, const float*, const float*,
-                        const float*, float*, hipStream_t);
-void conv3x3_c128_launch(int, int, int, int, const void*, const void*, int, void*, void*,
-                         const void*, const void*, const float*, const float*, float*, float*,
-                         hipStream_t);
-void maxpool_fwd_launch(int, int, int, int, const void*, void*, void*, hipStream_t);
-void maxpool_bn_fwd_launch(int, int, int, int, const void*, const float*, void*, void*, hipStream_t);
-int maxpool_bn_bwd_rows(int, int, int, int);
-void maxpool_bn_bwd_launch(int, int, int, int, const void*, const void*, const void*, const float*,
-                           const float*, const float*, const float*, float*, float*, float*,
-                           void*, void*, float*, hipStream_t);
-void maxpool_bwd_launch(int, int, int, int, const void*, const void*, void*, hipStream_t);
-void avgpool_fwd_launch(int, int, int, const void*, void*, hipStream_t);
-void avgpool_bwd_launch(int, int, int, const void*, void*, hipStream_t);
-void sgd_momentum_mixed_launch(long long, float*, const float*, float*, void*, float, float, float,
-                               float, hipStream_t, const long long*, int);
-void layernorm_fwd_launch(int, int, const void*, const float*, const float*, float, void*, float*,
-                          float*, hipStream_t);
-void layernorm_bwd_launch(int, int, const void*, const void*, const float*, const float*,
-                          const float*, const void*, void*, float*, float*, float*, hipStream_t);
-void embed_ln_fwd_launch(int, int, int, const int*, const int*, const void*, const void*,
-                         const void*, const float*, const float*, float, void*, void*, float*,
-                         float*, hipStream_t);
-void embed_bwd_launch(int, int, int, const int*, const int*, const void*, float*, float*, float*,
-                      hipStream_t);
-void attn_fwd_launch(int, int, int, const void*, void*, float*, const float*, float, hipStream_t);
-void attn_bwd_launch(int, int, int, const void*, const void*, const void*, const float*,
-                     const float*, float, void*, float*, hipStream_t);
-void adam_mixed_launch(long long, float*, const float*, float*, float*, void*, float, float, float,
-                       float, float, float, const int*, int, hipStream_t, const long long*, int,
-                       long long);
-void cast_f32_bf16_launch(long long, const float*, void*, hipStream_t);
-void zero_ranges_launch(const long long*, int, long long, hipStream_t);
-void act_grad_bf16_launch(long long, int, const void*, const void*, void*, hipStream_t);
-void flash_fwd_launch(int, int, int, const void*, void*, float*, int, const float*, float,
-                      hipStream_t);
-void flash_bwd_launch(int, int, int, const void*, const void*, const void*, const float*, int,
-                      const float*, float, void*, float*, float*, hipStream_t);
-void mlm_xent_launch(int, int, const void*, bool, int, const int*, float, float*, float*, void*, int,
-                     hipStream_t);
-}  // namespace dtfx
+namespace py = pybind11;
 
 template <typename T>
 static inline T* P(uintptr_t a) { return reinterpret_cast<T*>(a); }

@@ -1,5 +1,6 @@
 // Calibration kernels for launch/boundary measurements (tools/mlp_microbench.py).
 #include "common.h"
+#include "f32_api.h"
 
 namespace dtfx {
 

@@ -5,35 +5,15 @@
 // atomics), global average pool fwd/bwd, and mixed-precision momentum SGD.
 // North-star config 4 of BASELINE.json (ResNet-50 synthetic ImageNet); the
 // reference itself has no convolutional model (worker.py:47-54).
-#include "common.h"
+#include "bf16.h"
 #include "bn_common.h"
+#include "nn_api.h"
 
 #include <algorithm>
 
 #include <stdexcept>
 
 namespace dtfx {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
-namespace cn {
-__device__ __forceinline__ float bf(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ void unpack8(const bf16x8& v, float* f) {
-#pragma unroll
-  for (int u = 0; u < 8; ++u) f[u] = bf((unsigned short)v[u]);
-}
-__device__ __forceinline__ bf16x8 pack8(const float* f) {
-  bf16x8 v;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) v[u] = (short)tobf(f[u]);
-  return v;
-}
-}  // namespace cn
-using namespace cn;
 
 // Column reduction of partial rows: out_s[c] += sum_r part_s[r][c] (and the same for q).
 // grid (ceil(C / 64), S): 64 channels x 4 row groups per block, one atomic per channel per block.

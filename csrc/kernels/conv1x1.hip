@@ -16,29 +16,19 @@
 // an MFMA lane's 4 accumulator rows are 4 CONSECUTIVE channels of one pixel: outputs and side
 // inputs move as 8-B vectors of NHWC rows, and a lane's statistics stay its own 4 channels
 // for the whole block.  Compute wave w owns 32 channels (2 MFMA row tiles) of the block's 256.
-#include "common.h"
+#include "bf16.h"
 #include "bn_common.h"
+#include "knob.h"
+#include "nn_api.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <stdexcept>
 
 namespace dtfx {
 namespace pw {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int NTW = 2, NW = 8;
 constexpr int NC = NW * NTW * 16;  // 256 channels per block
-
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf(short v) {
-  return __uint_as_float((unsigned)(unsigned short)v << 16);
-}
 
 // Forward with a loader wave: wave NW (the ninth) only moves 64-pixel x tiles into a ring of
 // 3 LDS buffers (global_load_lds, counted vmcnt), the 8 compute waves only read LDS and store.
@@ -747,10 +737,8 @@ __global__ __launch_bounds__(256) void transpose_bf16_batch_kernel(const long lo
 }  // namespace pw
 
 static bool conv1x1_narrow(int K, int N) {
-  static const bool on = [] {  // DTFX_CONV1X1_NARROW=0: reductions stay on the implicit GEMM
-    const char* e = std::getenv("DTFX_CONV1X1_NARROW");
-    return !(e && std::atoi(e) == 0);
-  }();
+  // DTFX_CONV1X1_NARROW=0: reductions stay on the implicit GEMM
+  static const bool on = env_int("DTFX_CONV1X1_NARROW", 1) != 0;
   return on && ((K == 256 && (N == 64 || N == 128)) || (K == 512 && N == 128));
 }
 

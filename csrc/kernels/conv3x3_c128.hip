@@ -20,15 +20,14 @@
 // MFMAs) was LDS-bandwidth-bound at ~2.3x its MFMA time (every A fragment read fed one MFMA).
 // The two K halves are summed through LDS after the last tap: wave (cb, 0) finalises pixel
 // groups 0-3, wave (cb, 1) groups 4-6, each writing the other's groups first.
-#include "common.h"
+#include "bf16.h"
+#include "nn_api.h"
 
 #include <algorithm>
 #include <stdexcept>
 
 namespace dtfx {
 namespace c3b {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C = 128, TH = 4, TW = 28, PH = TH + 2, PW = TW + 2;  // 6 x 30 patch
 constexpr int NPX = TH * TW;                                      // 112 = 7 groups of 16
@@ -41,12 +40,6 @@ constexpr int WT_BYTES = C * WT_PITCH;                            // 34816 per t
 constexpr int R_BYTES = 4 * 2 * 7 * 64 * 16;                       // K-half partials 57344
 constexpr int S_BYTES = R_BYTES > P_BYTES ? R_BYTES : P_BYTES;     // patch / partials / staging
 constexpr int LDS = S_BYTES + 2 * WT_BYTES;                       // 126976
-
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float bf(short h) { return __uint_as_float((unsigned)(unsigned short)h << 16); }
 
 // W' [ci][tap * 128 + co] = W [co][(8 - tap) * 128 + ci]
 __global__ __launch_bounds__(256) void conv3x3_c128_flip_kernel(const unsigned short* __restrict__ w,

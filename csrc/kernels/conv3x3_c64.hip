@@ -13,15 +13,14 @@
 // k-group kg = (tap kg / 2, channel half kg % 2): 18 groups of 32; the wave layout of the
 // forward / data gradient is at conv3x3_c64_kernel, the weight gradient's at its kernel (which
 // keeps 4 x 28 tiles).
-#include "common.h"
+#include "bf16.h"
+#include "nn_api.h"
 
 #include <algorithm>
 #include <stdexcept>
 
 namespace dtfx {
 namespace c3 {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C = 64, TH = 4, TW = 28, PH = TH + 2, PW = TW + 2;  // 6 x 30 patch
 constexpr int NPX = TH * TW;                                     // 112 = 7 groups of 16
@@ -34,11 +33,6 @@ constexpr int TH2 = 8, NPX2 = TH2 * TW;                          // 224 = 14 gro
 constexpr int PCH2 = (TH2 + 2) * PW * 8;                         // 2400 patch chunks
 constexpr int PP2 = 144;                                         // patch pixel pitch (bytes)
 constexpr int R_BYTES = 2 * 2 * 2 * 7 * 64 * 16;                 // 57344 (> the 43200-B patch)
-
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
 
 // Forward (DGRAD false) and data gradient (DGRAD true) on 8 x 28-pixel output tiles (14
 // pixel groups of 16, a 10 x 30 input patch).  8 waves: wave w owns output channels
@@ -304,10 +298,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_c64_kernel(
 constexpr int DP = 144;  // dy tile row pitch (bytes)
 
 __device__ __forceinline__ bf16x8 tr_pair(const char* a0, const char* a1) {
-  typedef short bf16x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) bf16x4 lds4;
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a0);
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a1);
+  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a0);
+  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a1);
   bf16x8 v;
   v.lo = lo;
   v.hi = hi;

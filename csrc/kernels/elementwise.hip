@@ -5,6 +5,7 @@
 //   act_fwd : y = act(x)          standalone activation (when not fused)
 // float4 grid-stride loops; scalar tail.
 #include "common.h"
+#include "f32_api.h"
 
 namespace dtfx {
 

@@ -16,40 +16,18 @@
 //             D = rowsum(dO * O) comes from flash_rowdot (one pass).
 // MFMA v_mfma_f32_16x16x32_bf16 throughout (operand fragments from LDS: ds_read_b128
 // for k-contiguous images, ds_read_b64_tr_b16 for k-strided ones).
-#include "common.h"
+#include "bf16.h"
+#include "nn_api.h"
 
 #include <stdexcept>
 
 namespace dtfx {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_b4;
 
 namespace fa {
 constexpr int D = 64, T = 64;           // head dim, tile rows
 constexpr int LD = D * 2 + 16;          // 144-B LDS rows (16-B pad)
 constexpr int TILE = T * LD;            // 9216 B
 
-__device__ __forceinline__ float bf(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
-__device__ __forceinline__ float rmax16(float v) {
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, false)));
-  return v;
-}
-__device__ __forceinline__ float rsum16(float v) {
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, false));
-  return v;
-}
 // (tile, batch*head) of this block: the tiles of one (batch, head) share its K/V (forward,
 // dq) or Q/dO (dkdv) stream, so they are given consecutive ids of ONE XCD (bijective XCD
 // remap of the linear block id) instead of the dispatcher's round robin, which put the tiles
@@ -59,22 +37,6 @@ __device__ __forceinline__ void tile_bh(int& tile, int& bh) {
   const int id = xcd_remap(blockIdx.y * nt + blockIdx.x, nt * gridDim.y);
   tile = id % nt;
   bh = id / nt;
-}
-// operand fragment from an LDS image (see transformer.hip lfrag)
-template <bool KC>
-__device__ __forceinline__ bf16x8 frag(const char* base, int o0, int k0, int lane) {
-  if (KC) return *(const bf16x8*)(base + (o0 + (lane & 15)) * LD + (k0 + 8 * (lane >> 4)) * 2);
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const char* a = base + (k0 + 8 * g + q) * LD + (o0 + 4 * p) * 2;
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4*)a);
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_b4*)(a + 4 * LD));
-  bf16x8 v;
-  v.lo = lo;
-  v.hi = hi;
-  return v;
-}
-__device__ __forceinline__ f32x4 mma(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 // A-operand fragment (k-contiguous) straight from global: rows r0 + (lane & 15) (clamped)
 __device__ __forceinline__ bf16x8 gfrag(const unsigned short* base, int ld, int r0, int rmax, int k0,
@@ -157,7 +119,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(int S, int nh,
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) s[j] = mma(qa[kk], frag<true>(Ks, 16 * j, 32 * kk, lane), s[j]);
+      for (int j = 0; j < 4; ++j) s[j] = mma(qa[kk], lfrag<true>(Ks, LD, 16 * j, 32 * kk, lane), s[j]);
     float km[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -172,7 +134,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(int S, int nh,
         s[j][r] = s[j][r] * scale + km[j];
         mx = fmaxf(mx, s[j][r]);
       }
-      mx = rmax16(mx);
+      mx = row16_max(mx);
       const float mn = fmaxf(m[r], mx);
       const float ms = mn == -INFINITY ? 0.f : mn;
       const float alpha = __expf(m[r] - ms);  // m = -inf -> 0
@@ -182,7 +144,7 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(int S, int nh,
         s[j][r] = __expf(s[j][r] - ms);
         sum += s[j][r];
       }
-      sum = rsum16(sum);
+      sum = row16_sum(sum);
       l[r] = l[r] * alpha + sum;
       m[r] = mn;
 #pragma unroll
@@ -192,9 +154,9 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(int S, int nh,
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8 pa = frag<true>(Ps[wave], 0, 32 * kk, lane);
+      const bf16x8 pa = lfrag<true>(Ps[wave], LD, 0, 32 * kk, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = mma(pa, frag<false>(Vs, 16 * j, 32 * kk, lane), o[j]);
+      for (int j = 0; j < 4; ++j) o[j] = mma(pa, lfrag<false>(Vs, LD, 16 * j, 32 * kk, lane), o[j]);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -290,8 +252,8 @@ __global__ __launch_bounds__(256) void flash_dkdv_kernel(
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        st[j] = mma(ka[kk], frag<true>(Qs, 16 * j, 32 * kk, lane), st[j]);
-        dpt[j] = mma(va[kk], frag<true>(dOs, 16 * j, 32 * kk, lane), dpt[j]);
+        st[j] = mma(ka[kk], lfrag<true>(Qs, LD, 16 * j, 32 * kk, lane), st[j]);
+        dpt[j] = mma(va[kk], lfrag<true>(dOs, LD, 16 * j, 32 * kk, lane), dpt[j]);
       }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -308,12 +270,12 @@ __global__ __launch_bounds__(256) void flash_dkdv_kernel(
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8 pa = frag<true>(PT[wave], 0, 32 * kk, lane);
-      const bf16x8 da = frag<true>(DT[wave], 0, 32 * kk, lane);
+      const bf16x8 pa = lfrag<true>(PT[wave], LD, 0, 32 * kk, lane);
+      const bf16x8 da = lfrag<true>(DT[wave], LD, 0, 32 * kk, lane);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        dv[j] = mma(pa, frag<false>(dOs, 16 * j, 32 * kk, lane), dv[j]);
-        dk[j] = mma(da, frag<false>(Qs, 16 * j, 32 * kk, lane), dk[j]);
+        dv[j] = mma(pa, lfrag<false>(dOs, LD, 16 * j, 32 * kk, lane), dv[j]);
+        dk[j] = mma(da, lfrag<false>(Qs, LD, 16 * j, 32 * kk, lane), dk[j]);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -398,8 +360,8 @@ __global__ __launch_bounds__(256) void flash_dq_kernel(
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s[j] = mma(qa[kk], frag<true>(Ks, 16 * j, 32 * kk, lane), s[j]);
-        dp[j] = mma(oa[kk], frag<true>(Vs, 16 * j, 32 * kk, lane), dp[j]);
+        s[j] = mma(qa[kk], lfrag<true>(Ks, LD, 16 * j, 32 * kk, lane), s[j]);
+        dp[j] = mma(oa[kk], lfrag<true>(Vs, LD, 16 * j, 32 * kk, lane), dp[j]);
       }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -415,9 +377,9 @@ __global__ __launch_bounds__(256) void flash_dq_kernel(
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8 da = frag<true>(DS[wave], 0, 32 * kk, lane);
+      const bf16x8 da = lfrag<true>(DS[wave], LD, 0, 32 * kk, lane);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) dq[j] = mma(da, frag<false>(Ks, 16 * j, 32 * kk, lane), dq[j]);
+      for (int j = 0; j < 4; ++j) dq[j] = mma(da, lfrag<false>(Ks, LD, 16 * j, 32 * kk, lane), dq[j]);
     }
     __builtin_amdgcn_wave_barrier();
   }

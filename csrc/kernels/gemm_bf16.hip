@@ -44,8 +44,9 @@
 // 16-byte aligned bases; M, N arbitrary (edge rows are clamped on load and
 // masked on store).
 #include "gemm_bf16_common.h"
+#include "knob.h"
+#include "nn_api.h"
 
-#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -878,16 +879,13 @@ __global__ __launch_bounds__(NBUF == 8 ? 512 : (BM_ / (BN_ == 256 ? 128 : 64)) *
 // schedule (128 KB) -- the default large tile.  Auto: by wave quantisation (choose_cfg).
 // DTFX_GEMM_CFG=0..5 or gemm_bf16_set_cfg() forces one (tests, benchmarks).
 // ---------------------------------------------------------------------------
-static int g_gemm_cfg = -2;  // -2: not read yet; -1: auto; 0..5 forced
-static int gemm_cfg_env() {
-  if (g_gemm_cfg == -2) {
-    const char* e = getenv("DTFX_GEMM_CFG");
-    g_gemm_cfg = e ? atoi(e) : -1;
-  }
-  return g_gemm_cfg;
-}
+static Knob g_gemm_cfg{"DTFX_GEMM_CFG", -1};  // -1: auto; 0..5 forced
+static int gemm_cfg_env() { return g_gemm_cfg.get(); }
 // Force a tile configuration (-1 = auto) for tests and A/B benchmarks in one process.
-void gemm_bf16_set_cfg(int cfg) { g_gemm_cfg = cfg; }
+void gemm_bf16_set_cfg(int cfg) {
+  if (cfg < 0) g_gemm_cfg.reset(-1);  // auto, whatever DTFX_GEMM_CFG says
+  else g_gemm_cfg.set(cfg);
+}
 
 static int choose_cfg(int M, int N, int zdim, int mode, bool ta = false) {
   const int f = gemm_cfg_env();
@@ -904,15 +902,10 @@ static int choose_cfg(int M, int N, int zdim, int mode, bool ta = false) {
     // DTFX_GEMM_TA8=1: weight gradients on the 8-phase tile too; =2: only the large ones
     // (>= 2 M outputs: BERT-base's FFN weight gradients, 808 vs 731 TFLOP/s standalone, while
     // the QKV one is slower there, 632 vs 730: profiles/r6/gemm/wgrad_cfg/)
-    static const int ta8 = [] {
-      const char* e = getenv("DTFX_GEMM_TA8");
-      return e ? atoi(e) : 0;
-    }();
+    static const int ta8 = env_int("DTFX_GEMM_TA8", 0);
     if (ta && (ta8 <= 0 || (ta8 == 2 && (long long)M * N < 2000000))) return 0;
-    static const int big = [] {  // DTFX_GEMM_BIG=3: the previous 2-stage large tile (A/B runs)
-      const char* e = getenv("DTFX_GEMM_BIG");
-      return e && atoi(e) == 3 ? 3 : 5;
-    }();
+    // DTFX_GEMM_BIG=3: the previous 2-stage large tile (A/B runs)
+    static const int big = env_int("DTFX_GEMM_BIG", 5) == 3 ? 3 : 5;
     const long long t3 = (long long)((M + 255) / 256) * ((N + 255) / 256) * zdim;
     const long long t6 = (long long)((M + 255) / 256) * ((N + 191) / 192) * zdim;
     const long long t0 = (long long)((M + 127) / 128) * ((N + 127) / 128) * zdim;
@@ -930,18 +923,13 @@ static int choose_cfg(int M, int N, int zdim, int mode, bool ta = false) {
     // stream, which use the 64 CUs a 192-block 256x256 grid leaves free (BERT-base, same box,
     // two rounds: 7928 / 7890 seq/s with cfg 5 vs 7697 / 7639 with cfg 6; without the second
     // stream both ~7840 -- scripts/gpu_bert_ab.sh)
-    static const bool use6 = [] {
-      const char* e = getenv("DTFX_GEMM_TILE192");
-      return e && atoi(e) == 1;
-    }();
+    static const bool use6 = env_int("DTFX_GEMM_TILE192", 0) == 1;
     if (use6 && est6 < est5 && est6 < est0 && N > 128) return 6;
     // vocabulary-wide outputs (BERT's MLM logits, 2432 x 30528 x 768): the model rates the
     // 128x128 tile 4 % ahead, the 8-phase tile measures 11 % ahead (735 vs 662 TFLOP/s,
     // profiles/r6/gemm/decoder/) -- within 10 % of the model, wide outputs take the big tile
-    static const bool wide5 = [] {  // DTFX_GEMM_WIDE=0: the model's choice (A/B runs)
-      const char* e = getenv("DTFX_GEMM_WIDE");
-      return !(e && atoi(e) == 0);
-    }();
+    // DTFX_GEMM_WIDE=0: the model's choice (A/B runs)
+    static const bool wide5 = env_int("DTFX_GEMM_WIDE", 1) != 0;
     if (wide5 && zdim == 1 && !ta && N >= 16384 && t3 >= 256 && est5 <= est0 * 1.1) return 5;
     // the 8-phase tile with its sparse last round's rows on the 128x128 tile (gemm_tail_rows):
     // the whole rounds plus the tail's 128x128 rounds (BERT-base QKV: 2 + 0.53 against the
@@ -981,17 +969,11 @@ static int choose_cfg(int M, int N, int zdim, int mode, bool ta = false) {
 // transpose and 128 KB of stores per block that the next tile's counted vmcnt waits out
 // (gfx9 counts stores and loads in one vmcnt), so a store-overlapping epilogue would need
 // separate store waves and LDS the 8-phase tile does not have free.
-static int g_gemm_pers = -1;  // -1: read DTFX_GEMM_PERS on first use
-static bool gemm_pers_on() {
-  if (g_gemm_pers < 0) {
-    const char* e = getenv("DTFX_GEMM_PERS");
-    g_gemm_pers = e && atoi(e) == 1 ? 1 : 0;
-  }
-  return g_gemm_pers == 1;
-}
+static Knob g_gemm_pers{"DTFX_GEMM_PERS", 0};
+static bool gemm_pers_on() { return g_gemm_pers.get() == 1; }
 int gemm_bf16_set_pers(int on) {  // tests / A/B in one process; returns the previous setting
   const int old = gemm_pers_on() ? 1 : 0;
-  g_gemm_pers = on ? 1 : 0;
+  g_gemm_pers.set(on ? 1 : 0);
   return old;
 }
 static int gemm_num_cus() {
@@ -1028,10 +1010,7 @@ static void launch_one(dim3 grid_yz, int M, int N, int K, const unsigned short* 
   // stage or the epilogue's per-wave transpose rows, whichever is larger -- three resident
   // 128x128 blocks per CU instead of two (ResNet-50 layer1 conv3 forward, K = 64: 236 -> 194
   // us; DTFX_GEMM_1STAGE=0: full stages)
-  static const bool one_stage_ok = [] {
-    const char* v = getenv("DTFX_GEMM_1STAGE");
-    return v ? atoi(v) != 0 : true;
-  }();
+  static const bool one_stage_ok = env_int("DTFX_GEMM_1STAGE", 1) != 0;
   size_t lds_launch = lds;
   if (NBUF == 2 && one_stage_ok && K <= gb::BK && grid_yz.y == 1) {
     const size_t stage = (size_t)(BM_ * gb::BK * 2 + BN_ * gb::BK * 2);
@@ -1322,10 +1301,7 @@ static int gemm_splitk(bool ta, bool out_f32, int M, int N, int K, int splitk, i
     // DTFX_GEMM_TA8_SLOTS: block slots a weight gradient on the 8-phase tile splits for
     // (DTFX_GEMM_TA8=1 A/B runs; fewer splits = fewer partial planes for the optimizer to read
     // while the data gradients hold the rest of the chip)
-    static const int ta8_slots = [] {
-      const char* e = getenv("DTFX_GEMM_TA8_SLOTS");
-      return e ? std::max(1, atoi(e)) : 256;
-    }();
+    static const int ta8_slots = std::max(1, env_int("DTFX_GEMM_TA8_SLOTS", 256));
     const int slots = cfg == 0 ? 512 : ta ? ta8_slots : 256;
     if (tiles < slots / 2) return std::max(1, std::min(slots / tiles, nkt / 8));
   }
@@ -1358,10 +1334,7 @@ static void gemm_bf16_launch_cfg(bool ta, bool tb, bool out_f32, int M, int N, i
 // epilogues only (bias / act / aux / residual; column sums accumulate from both parts);
 // DTFX_GEMM_TAILSPLIT=0 turns it off.  Returns the rows left for the 8-phase part (M: none).
 static int gemm_tail_rows(int M, int N, int cfg, bool ta, int splitk, int batch) {
-  static const bool on = [] {
-    const char* e = getenv("DTFX_GEMM_TAILSPLIT");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool on = env_int("DTFX_GEMM_TAILSPLIT", 1) != 0;
   if (!on || cfg != 5 || ta || splitk > 1 || batch != 1) return M;
   const int tm = (M + 255) / 256, tn = (N + 255) / 256;
   const long long T = (long long)tm * tn;
@@ -1484,20 +1457,14 @@ static void gemm_bf16_launch_cfg(bool ta, bool tb, bool out_f32, int M, int N, i
 // 525 us and 426 -> 548 us on the 8-phase tile; layer3 3x3 forward, K = 2304: 120 -> 74 us).
 // DTFX_CONV_PH8=0 keeps every convolution on the 128x128 / 256x64 tiles (A/B runs).
 static bool conv_ph8(int M, int N, int K, int zdim, int src_ch, long long src_elems) {
-  static const bool on = [] {
-    const char* v = getenv("DTFX_CONV_PH8");
-    return v ? atoi(v) != 0 : true;
-  }();
+  static const bool on = env_int("DTFX_CONV_PH8", 1) != 0;
   return on && K >= 4 * gb::BK && src_ch % 64 == 0 && src_elems * 2 < 0x7fffffffLL &&
          choose_cfg(M, N, zdim, 0) == 5;
 }
 
 // cfg 5 -> 7 for a 1x1 / stride-1 / pad-0 convolution (the F1 staging; DTFX_CONV_F1=0: off)
 static int conv_f1(int cfg, int KH, int KW, int stride, int pad) {
-  static const bool on = [] {
-    const char* v = getenv("DTFX_CONV_F1");
-    return v ? atoi(v) != 0 : true;
-  }();
+  static const bool on = env_int("DTFX_CONV_F1", 1) != 0;
   return on && cfg == 5 && KH == 1 && KW == 1 && stride == 1 && pad == 0 ? 7 : cfg;
 }
 
@@ -1508,10 +1475,7 @@ static int conv_f1(int cfg, int KH, int KW, int stride, int pad) {
 // DTFX_CONV_SPLITK=0 disables (A/B runs).
 int conv_splitk(int mode, int N, int H, int W, int C, int Cout, int KH, int KW, int stride,
                 int pad) {
-  static const bool on = [] {
-    const char* v = getenv("DTFX_CONV_SPLITK");
-    return v ? atoi(v) != 0 : true;
-  }();
+  static const bool on = env_int("DTFX_CONV_SPLITK", 1) != 0;
   if (!on || gemm_cfg_env() >= 0 || (mode != 1 && !(mode == 2 && stride == 1))) return 1;
   const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   const int M = mode == 1 ? N * OH * OW : N * H * W, Nn = mode == 1 ? Cout : C;
@@ -1536,10 +1500,7 @@ long long conv_splitk_ws_floats(int mode, int N, int H, int W, int C, int Cout, 
 // 128x128 tile these ran at 470-530 TFLOP/s (LDS-bound: 2 x 8 KB of fragments per 128x128x64
 // step).  DTFX_CONV_WGRAD_PH8=0 keeps them there (A/B runs).
 static bool conv_wgrad_ph8(int M, int Nn, int K, long long src_elems) {
-  static const bool on = [] {
-    const char* v = getenv("DTFX_CONV_WGRAD_PH8");
-    return v ? atoi(v) != 0 : true;
-  }();
+  static const bool on = env_int("DTFX_CONV_WGRAD_PH8", 1) != 0;
   return on && gemm_cfg_env() < 0 && M >= 256 && K % gb::BK == 0 && Nn >= 256 &&
          src_elems * 2 < 0x7fffffffLL;
 }
@@ -1600,10 +1561,8 @@ void conv_bf16_launch(int mode, int N, int H, int W, int C, int Cout, int KH, in
     M = N * OH * OW; Nn = Cout; K = d.ktot;
     if (ldw < (K + 63) / 64 * 64) throw std::runtime_error("conv_bf16: fwd weights need ld >= ceil64(KH*KW*C)");
     e.ld_res = Cout;
-    static const int plain1x1 = [] {  // DTFX_CONV1X1_GEMM=0: keep 1x1 convs on the gather path
-      const char* v = getenv("DTFX_CONV1X1_GEMM");
-      return v ? atoi(v) : 1;
-    }();
+    // DTFX_CONV1X1_GEMM=0: keep 1x1 convs on the gather path
+    static const int plain1x1 = env_int("DTFX_CONV1X1_GEMM", 1);
     if (plain1x1 && KH == 1 && KW == 1 && stride == 1 && pad == 0 && C % 64 == 0 && C >= 256) {
       // a 1x1 stride-1 convolution is the plain GEMM y[M][Cout] = x[M][C] W[Cout][C]^T:
       // the 8-phase 256x256 tile when the time model picks it (partial statistic rows per
@@ -1708,10 +1667,8 @@ void conv_bf16_launch(int mode, int N, int H, int W, int C, int Cout, int KH, in
       throw std::runtime_error("conv_bf16: defer_reduce needs the exact split-K workspace "
                                "(conv_wgrad_ws_floats)");
     if (use_ws) e.ws = ws;
-    static const bool plain1x1w = [] {  // DTFX_CONV1X1_WGRAD_GEMM=0: 1x1 wgrads on the gather path
-      const char* v = getenv("DTFX_CONV1X1_WGRAD_GEMM");
-      return v ? atoi(v) != 0 : true;
-    }();
+    // DTFX_CONV1X1_WGRAD_GEMM=0: 1x1 wgrads on the gather path
+    static const bool plain1x1w = env_int("DTFX_CONV1X1_WGRAD_GEMM", 1) != 0;
     if (plain1x1w && KH == 1 && KW == 1 && stride == 1 && pad == 0 && K % gb::BK == 0) {
       // a 1x1 stride-1 weight gradient is the plain product dW[co][ci] = sum_p dy[p][co] x[p][ci]
       // (A^T B, both operands k-strided): staged by the plain glds loader instead of the
@@ -1792,8 +1749,8 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const unsigned short* 
   }
 }
 
-static int g_colsum_u = 0;  // 0: DTFX_COLSUM_U; 4 / 8 forced (tests, probes)
-void colsum_set_rows_in_flight(int u) { g_colsum_u = (u == 4 || u == 8) ? u : 0; }
+static Knob g_colsum_u{"DTFX_COLSUM_U", 4};  // 4 / 8 forced (tests, probes)
+void colsum_set_rows_in_flight(int u) { g_colsum_u.set((u == 4 || u == 8) ? u : -1); }
 
 void colsum_bf16_launch(const void* G, int M, int N, int ldg, float* out, float beta,
                         hipStream_t stream) {
@@ -1808,11 +1765,7 @@ void colsum_bf16_launch(const void* G, int M, int N, int ldg, float* out, float 
     if (beta == 0.f) DTFX_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(float) * N, stream));
     else if (beta != 1.f) throw std::runtime_error("colsum_bf16: beta must be 0 or 1 for tall inputs");
   }
-  static const int u_env = [] {
-    const char* e = getenv("DTFX_COLSUM_U");
-    return e && atoi(e) == 8 ? 8 : 4;
-  }();
-  const int u = g_colsum_u > 0 ? g_colsum_u : u_env;
+  const int u = g_colsum_u.get() == 8 ? 8 : 4;
   if (vec && u == 8)
     hipLaunchKernelGGL(colsum8_bf16_kernel<8>, dim3(gx, gy), dim3(256), 0, stream,
                        (const unsigned short*)G, M, N, ldg, out, beta);

@@ -4,21 +4,16 @@
 // probes under tools/probes/ build variants of the tile schedules on the same primitives.
 #pragma once
 
-#include "common.h"
+#include "bf16.h"
 
 namespace dtfx {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 
-__device__ __forceinline__ float bf2f(unsigned short h) {
-  return __uint_as_float((unsigned)h << 16);
-}
-__device__ __forceinline__ unsigned short f2bf(float f) {
-  __bf16 b = (__bf16)f;  // v_cvt_pk_bf16_f32: round-to-nearest-even, NaN stays NaN
-  return __builtin_bit_cast(unsigned short, b);
-}
+// the GEMM family's names for bf16.h's bf / tobf (v_cvt_pk_bf16_f32: round-to-nearest-even, NaN
+// stays NaN)
+__device__ __forceinline__ float bf2f(unsigned short h) { return bf(h); }
+__device__ __forceinline__ unsigned short f2bf(float f) { return tobf(f); }
 
 // GELU (tanh form) and its derivative, as sigmoids: 0.5 (1 + tanh(u)) = sigmoid(2u), so
 //   gelu(x)  = x * s,  s = 1 / (1 + 2^(-x (A + B x^2)))   (A, B: 2 sqrt(2/pi) (1, 0.044715),

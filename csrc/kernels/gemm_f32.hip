@@ -20,6 +20,7 @@
 // The next K tile is prefetched into registers while the current one is
 // consumed.  Block ids are XCD-remapped so neighbouring tiles share an L2.
 #include "common.h"
+#include "f32_api.h"
 
 #include <stdexcept>
 #include <string>

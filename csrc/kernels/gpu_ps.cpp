@@ -20,6 +20,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "gpu_ps.h"
+
 namespace py = pybind11;
 
 #define GPS_CHECK(expr)                                                                \
@@ -31,18 +33,6 @@ namespace py = pybind11;
   } while (0)
 
 namespace dtfx {
-
-void gps_pull_launch(float*, const float*, long long, hipStream_t);
-void gps_apply_launch(float*, const float*, float, long long, bool, hipStream_t);
-void gps_fetch_add_launch(unsigned long long*, long long, unsigned long long*, const float*, int,
-                          hipStream_t);
-void gps_sync_join_launch(unsigned long long*, unsigned, unsigned, unsigned*, const float*, int,
-                          hipStream_t);
-void gps_sync_push_launch(float*, float*, long long, const float*, const unsigned*, unsigned*,
-                          unsigned*, unsigned long long*, unsigned long long*, float, unsigned,
-                          long long, int, float*, float*, float, float, float, hipStream_t);
-void gps_apply_opt_launch(float*, float*, float*, const float*, const unsigned long long*, float,
-                          int, float, float, float, long long, hipStream_t);
 
 class GpuParamStore {
  public:

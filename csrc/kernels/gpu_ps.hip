@@ -20,6 +20,7 @@
 //   gps_sync_join / gps_sync_push   --sync_replicas: ticket of the open round, gradient into the
 //                     ticket's slot; the R-th arrival of a chunk applies the mean (below)
 #include "common.h"
+#include "gpu_ps.h"
 
 #include <stdexcept>
 

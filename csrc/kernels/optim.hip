@@ -11,6 +11,7 @@
 // `lr_ptr` / `step_ptr` (optional) let a captured hipGraph pick up a device-side
 // learning-rate schedule / step count instead of a frozen kernel argument.
 #include "common.h"
+#include "f32_api.h"
 
 #include <stdexcept>
 

@@ -19,6 +19,7 @@
 // read once (non-temporal loads); destination rows are what the next epoch's steps read (plain
 // stores).  The grid is capped and strides over the rows.
 #include "common.h"
+#include "f32_api.h"
 
 #include <stdexcept>
 

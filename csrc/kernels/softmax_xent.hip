@@ -8,6 +8,7 @@
 // accuracy of worker.py:89-90 (argmax(softmax) == argmax(y), first max wins)
 // is fused in: argmax(softmax(l)) = argmax(l).
 #include "common.h"
+#include "f32_api.h"
 
 #include <stdexcept>
 

@@ -13,15 +13,14 @@
 // MFMA v_mfma_f32_16x16x32_bf16: k-group kg = taps 4kg..4kg+3 x 8 channels (13 groups, taps
 // 49-51 zero weights); wave w owns output rows 2w, 2w+1 of the tile (2 x 16 pixels) x 64
 // channels = 2 x 4 accumulator tiles.
-#include "common.h"
+#include "bf16.h"
+#include "nn_api.h"
 
 #include <algorithm>
 #include <stdexcept>
 
 namespace dtfx {
 namespace stem {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int KS = 7, STR = 2, PAD = 3, CIN = 8, COUT = 64;
 constexpr int TH = 8, TW = 16;                                  // output tile
@@ -30,11 +29,6 @@ constexpr int NKG = 13;                                        // k-groups of 4 
 constexpr int WP = 456;                                        // weight row pitch (bf16): 912 B
 constexpr int W_BYTES = COUT * WP * 2;                         // 58368
 constexpr int P_BYTES = 16384;  // patch (777 x 16 B) / output staging (4 waves x 32 px x 128 B)
-
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
-}
 
 // Forward tiles: 16 x 16 output pixels, wave w owns output rows 4w..4w+3 (4 A fragments of
 // 16 pixels) x 64 channels (4 B fragments): 8 LDS fragment reads per 16 MFMAs (the first
@@ -181,10 +175,8 @@ __global__ __launch_bounds__(256, 2) void stem_conv_fwd_kernel(
 constexpr int DP = 144;  // dy tile row pitch (bytes)
 
 __device__ __forceinline__ bf16x8 tr_pair(const char* a0, const char* a1) {
-  typedef short bf16x4 __attribute__((ext_vector_type(4)));
-  typedef __attribute__((address_space(3))) bf16x4 lds4;
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a0);
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a1);
+  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a0);
+  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a1);
   bf16x8 v;
   v.lo = lo;
   v.hi = hi;

@@ -9,79 +9,19 @@
 // reads the fused QKV projection output [T][3*Hd] in place (head h of Q at
 // columns h*64, of K at Hd + h*64, of V at 2*Hd + h*64) and writes its
 // gradient into the same layout, so no transpose/permute pass exists.
-#include "common.h"
+#include "bf16.h"
+#include "knob.h"
+#include "nn_api.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
-#include <string>
 
 namespace dtfx {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-
-namespace tf {
-
-__device__ __forceinline__ float bf(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short tobf(float f) {
-  __bf16 b = (__bf16)f;
-  return __builtin_bit_cast(unsigned short, b);
+static void check_h(int H) {
+  if (H % 8 || H > 2048) throw std::runtime_error("transformer: H must be a multiple of 8 and <= 2048");
 }
-__device__ __forceinline__ float tobf_round(float f) { return bf(tobf(f)); }
-__device__ __forceinline__ void unpack8(const bf16x8& v, float* f) {
-#pragma unroll
-  for (int u = 0; u < 8; ++u) f[u] = bf((unsigned short)v[u]);
-}
-__device__ __forceinline__ bf16x8 pack8(const float* f) {
-  bf16x8 v;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) v[u] = (short)tobf(f[u]);
-  return v;
-}
-
-// Reductions inside one 16-lane DPP row (the 16 lanes of an MFMA C/D tile that
-// share a row group).
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, false)));
-  return v;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x124, 0xF, 0xF, false));
-  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xF, 0xF, false));
-  return v;
-}
-
-// MFMA 16x16x32 bf16 operand fragment from an LDS matrix with row pitch `ld`
-// bytes: lane gets X[outer = o0 + (lane & 15)][k = k0 + 8 (lane >> 4) + j].
-//  KC : element (outer, k) at base + outer*ld + 2k   (one ds_read_b128)
-//  !KC: element (outer, k) at base + k*ld + 2*outer  (two ds_read_b64_tr_b16)
-template <bool KC>
-__device__ __forceinline__ bf16x8 lfrag(const char* base, int ld, int o0, int k0, int lane) {
-  if (KC) {
-    return *(const bf16x8*)(base + (o0 + (lane & 15)) * ld + (k0 + 8 * (lane >> 4)) * 2);
-  } else {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const char* a = base + (k0 + 8 * g + q) * ld + (o0 + 4 * p) * 2;
-    bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)a);
-    bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(a + 4 * ld));
-    bf16x8 v;
-    v.lo = lo;
-    v.hi = hi;
-    return v;
-  }
-}
-__device__ __forceinline__ f32x4 mma(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-}  // namespace tf
-
-using namespace tf;
 
 // ---------------------------------------------------------------------------
 // LayerNorm: one wave per row, H % 8 == 0, H <= 2048 (<= 4 16-B chunks/lane)
@@ -202,6 +142,36 @@ __global__ __launch_bounds__(256) void layernorm_fwd_rows_kernel(
       rstd_out[row] = rstd;
     }
   }
+}
+
+void layernorm_fwd_launch(int T, int H, const void* x, const float* gamma, const float* beta,
+                          float eps, void* y, float* mean, float* rstd, hipStream_t s) {
+  check_h(H);
+  if (T <= 0) return;
+  // rows per wave (DTFX_LN_FWD_ROWS=1: the one-row kernel, for A/B runs)
+  static const int rows = [] {
+    const char* e = getenv("DTFX_LN_FWD_ROWS");
+    return e ? atoi(e) : 4;
+  }();
+  const auto* xs = (const unsigned short*)x;
+  auto* ys = (unsigned short*)y;
+  const int nc = (H + 511) / 512;
+  if ((rows == 4 || rows == 2) && !(((uintptr_t)gamma | (uintptr_t)beta) & 15)) {  // (f32x4 gamma / beta)
+    const int per_block = 4 * rows;
+    const dim3 grid((T + per_block - 1) / per_block);
+#define DTFX_LNF(NC_, R_) \
+  hipLaunchKernelGGL((layernorm_fwd_rows_kernel<NC_, R_>), grid, dim3(256), 0, s, T, H, xs, gamma, beta, eps, ys, mean, rstd)
+    if (rows == 4) {
+      if (nc == 1) DTFX_LNF(1, 4); else if (nc == 2) DTFX_LNF(2, 4); else if (nc == 3) DTFX_LNF(3, 4); else DTFX_LNF(4, 4);
+    } else {
+      if (nc == 1) DTFX_LNF(1, 2); else if (nc == 2) DTFX_LNF(2, 2); else if (nc == 3) DTFX_LNF(3, 2); else DTFX_LNF(4, 2);
+    }
+#undef DTFX_LNF
+  } else {
+    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, T, H, xs, gamma, beta, eps,
+                       ys, mean, rstd);
+  }
+  DTFX_HIP_CHECK(hipGetLastError());
 }
 
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma
@@ -445,6 +415,58 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   }
 }
 
+// (these two knobs, DTFX_LN_FWD_ROWS above and DTFX_ATTN_BWD_BLOCKS below keep the hand-written
+// form instead of knob.h's: tests/transformer_reference.py launch_constants() reads their text)
+static int g_ln_slots = -1;  // -1: DTFX_LN_SLOTS (tests set both forms)
+void ln_bwd_set_slots(int v) { g_ln_slots = v; }
+static int g_ln_h768 = -1;  // -1: DTFX_LN_H768
+void ln_bwd_set_h768(int v) { g_ln_h768 = v; }
+
+void layernorm_bwd_launch(int T, int H, const void* dy, const void* x, const float* mean,
+                          const float* rstd, const float* gamma, const void* dres, void* dx,
+                          float* dgamma, float* dbeta, float* dxsum, hipStream_t s) {
+  check_h(H);
+  if (T <= 0) return;
+  // BERT 16384 rows: 256 blocks (measured 16: 54 us, 32: 35, 64: 31, 128: 38 -- atomics vs
+  // parallelism; with two rows in flight per wave 32: 33.9, 64: 26.5, 128: 29.8 us).  DTFX_LN_RPB overrides (sweeps).
+  static const int rpb_env = env_int("DTFX_LN_RPB", 0);
+  static const int slots_env = [] {
+    const char* e = getenv("DTFX_LN_SLOTS");
+    return e ? std::max(1, std::min(3, atoi(e))) : 2;
+  }();
+  // row slots per wave of the generic kernel: 2 (default) or 3
+  const int slots = g_ln_slots >= 0 ? std::max(1, std::min(3, g_ln_slots)) : slots_env;
+  static const int h768_env = [] {
+    const char* e = getenv("DTFX_LN_H768");
+    return e ? atoi(e) : 0;
+  }();
+  if (H == 768 && (g_ln_h768 >= 0 ? g_ln_h768 : h768_env) == 1 && !(((uintptr_t)gamma) & 15)) {
+    // 4 rows per wave at the BERT shape (512 blocks, two per CU)
+    const int rpb7 = rpb_env > 0 ? rpb_env : (T >= 8192 ? 32 : 8);
+    // one row slot per wave: the 16 resident waves per CU are the pipeline (two slots spill
+    // at the 128 VGPRs four waves per SIMD allow)
+    hipLaunchKernelGGL(layernorm_bwd_h768_kernel<1>, dim3((T + rpb7 - 1) / rpb7), dim3(512), 0, s,
+                         T, rpb7, (const unsigned short*)dy, (const unsigned short*)x, mean, rstd,
+                         gamma, (const unsigned short*)dres, (unsigned short*)dx, dgamma, dbeta, dxsum);
+    DTFX_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  const int rpb = rpb_env > 0 ? rpb_env : (T >= 8192 ? 64 : 16);
+  const int nc = (H / 8 + 63) / 64;
+#define DTFX_LNB(NC_, NS_)                                                                      \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<NC_, NS_>), dim3((T + rpb - 1) / rpb), dim3(NC_ <= 2 ? 512 : 256), 0, s, T, H, \
+                     rpb, (const unsigned short*)dy, (const unsigned short*)x, mean, rstd, gamma,  \
+                     (const unsigned short*)dres, (unsigned short*)dx, dgamma, dbeta, dxsum)
+  if (nc == 1 && slots >= 3) DTFX_LNB(1, 3);
+  else if (nc == 2 && slots >= 3) DTFX_LNB(2, 3);
+  else if (nc == 1) DTFX_LNB(1, 2);
+  else if (nc == 2) DTFX_LNB(2, 2);
+  else if (nc == 3) DTFX_LNB(3, 2);
+  else DTFX_LNB(4, 2);
+#undef DTFX_LNB
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------
 // Embedding: x = word[ids] + pos[t % S] + type[tt]; y = LN(x).  Saves x (bf16).
 // ---------------------------------------------------------------------------
@@ -502,6 +524,18 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(
     mean_out[row] = mean;
     rstd_out[row] = rstd;
   }
+}
+
+void embed_ln_fwd_launch(int T, int S, int H, const int* ids, const int* tt, const void* word,
+                         const void* pos, const void* type, const float* gamma, const float* beta,
+                         float eps, void* xsum, void* y, float* mean, float* rstd, hipStream_t s) {
+  check_h(H);
+  if (T <= 0) return;
+  hipLaunchKernelGGL(embed_ln_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, T, S, H, ids, tt,
+                     (const unsigned short*)word, (const unsigned short*)pos,
+                     (const unsigned short*)type, gamma, beta, eps, (unsigned short*)xsum,
+                     (unsigned short*)y, mean, rstd);
+  DTFX_HIP_CHECK(hipGetLastError());
 }
 
 // word-embedding gradient: scatter-add of dx rows (f32 hardware atomics; ids are
@@ -585,6 +619,19 @@ __global__ __launch_bounds__(1024) void embed_pos_type_bwd_kernel(
   }
 }
 
+void embed_bwd_launch(int Bn, int S, int H, const int* ids, const int* tt, const void* dx,
+                      float* dword, float* dpos, float* dtype_, hipStream_t s) {
+  check_h(H);
+  const int T = Bn * S;
+  if (T <= 0) return;
+  hipLaunchKernelGGL(embed_word_bwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, T, H, ids,
+                     (const unsigned short*)dx, dword);
+  DTFX_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(embed_pos_type_bwd_kernel, dim3(S), dim3(1024), 0, s, Bn, S, H, tt,
+                     (const unsigned short*)dx, dpos, dtype_);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------
 // Self-attention, one workgroup (4 waves) per (sequence b, head h), S <= 128,
 // head dim 64.  Q, K, V (and dO) tiles live in LDS with 144-B rows (16-B pad:
@@ -645,7 +692,7 @@ __device__ __forceinline__ void load_heads(char* const (&dst)[N], const unsigned
     }
 }
 
-// lfrag over a swizzled image (same lane map as tf::lfrag).  swz is XOR-linear in the row's
+// lfrag over a swizzled image (same lane map as lfrag).  swz is XOR-linear in the row's
 // low 4 bits and every fragment's first row is a multiple of 16 (row reads) or of 8 with the
 // lane's rows fixed modulo 16 (tr reads), so each lane's chunk XORs are constants computed once
 // (SwLane): a row read is one immediate offset, a tr read one XOR per fragment.
@@ -696,9 +743,20 @@ __device__ __forceinline__ int img_off(int r, int col) {
 template <bool SWZ, bool KC>
 __device__ __forceinline__ bf16x8 img_frag(const char* base, int o0, int k0, int lane) {
   if constexpr (SWZ) return lfrag_sw<KC>(base, o0, k0, lane);
-  else return tf::lfrag<KC>(base, LDQ, o0, k0, lane);
+  else return dtfx::lfrag<KC>(base, LDQ, o0, k0, lane);
 }
 }  // namespace at
+
+static void check_attn(int S, int nh) {
+  if (S <= 0 || S > at::SP) throw std::runtime_error("attention: fused kernel needs 0 < S <= 128");
+  if (nh <= 0) throw std::runtime_error("attention: nh must be positive");
+}
+
+// Swizzled attention images (opt-in, measured slower: see attn_fwd_kernel): -1 = from the
+// environment (DTFX_ATTN_SWZ=1), 0 / 1 forced (tests run both in one process).
+static Knob g_attn_swz{"DTFX_ATTN_SWZ", 0};
+void attn_set_swizzle(int v) { g_attn_swz.set(v); }
+static bool attn_swz() { return g_attn_swz.get() == 1; }
 
 // Q never goes through LDS: each wave's 32 query rows are only its own A operands, read
 // as MFMA fragments straight from global memory (issued before the K/V staging).  K, V
@@ -941,6 +999,48 @@ __global__ __launch_bounds__(256, 4) void attn_fwd_rp_kernel(
       if (row < S) *(bf16x8*)(out + ((size_t)b * S + row) * Hd + h * D + ch * 8) = v;
     }
   }
+}
+
+template <bool SWZ>
+static void attn_fwd_launch_t(int Bn, int S, int nh, const void* qkv, void* out, float* lse,
+                              const float* kmask, float scale, hipStream_t s) {
+  const size_t lds = 2 * (size_t)at::SP * at::img_pitch<SWZ>() + at::PB;
+  static bool attr = false;
+  if (!attr) {
+    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<SWZ>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  hipLaunchKernelGGL(attn_fwd_kernel<SWZ>, dim3(Bn * nh), dim3(256), lds, s, S, nh,
+                     (const unsigned short*)qkv, (unsigned short*)out, lse, kmask, scale);
+}
+
+// Attention forward: -1 = from DTFX_ATTN_FWD (default 1; only 0 turns it off), 1:
+// attn_fwd_rp_kernel (P in registers), any other forced value: attn_fwd_kernel (P through LDS;
+// DTFX_ATTN_SWZ picks its swizzled variant)
+static Knob g_attn_fwd{"DTFX_ATTN_FWD", 1};
+void attn_fwd_set_variant(int v) { g_attn_fwd.set(v < 0 ? -1 : v == 1); }
+static bool attn_fwd_rp() { return g_attn_fwd.get() != 0; }
+
+void attn_fwd_launch(int Bn, int S, int nh, const void* qkv, void* out, float* lse,
+                     const float* kmask, float scale, hipStream_t s) {
+  check_attn(S, nh);
+  if (attn_fwd_rp()) {
+    constexpr size_t lds = 2 * (size_t)at::QB + (size_t)at::SP * 4;
+    static bool attr = false;
+    if (!attr) {
+      DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_rp_kernel,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      attr = true;
+    }
+    hipLaunchKernelGGL(attn_fwd_rp_kernel, dim3(Bn * nh), dim3(256), lds, s, S, nh,
+                       (const unsigned short*)qkv, (unsigned short*)out, lse, kmask, scale);
+  } else if (attn_swz()) {
+    attn_fwd_launch_t<true>(Bn, S, nh, qkv, out, lse, kmask, scale, s);
+  } else {
+    attn_fwd_launch_t<false>(Bn, S, nh, qkv, out, lse, kmask, scale, s);
+  }
+  DTFX_HIP_CHECK(hipGetLastError());
 }
 
 // NW waves per (sequence, head): 4 (32 query / key rows per wave) or 8 (16 rows per wave:
@@ -1522,134 +1622,99 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_half_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------
-// Mixed-precision Adam(W): f32 master p, grad g, moments m, v; writes the bf16
-// working copy pb used by the GEMMs.  Grad scale folds the 1/world average.  p, m, v are
-// streamed (non-temporal: next read a whole step later), the bf16 copy is stored normally
-// (BERT-base +1.0 % together with the GEMMs' non-temporal f32 / split-K stores,
-// profiles/r5/gemm_nt/nt2/).
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_mixed_kernel(
-    long long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    float* __restrict__ v, unsigned short* __restrict__ pb, float lr, float b1, float b2,
-    float eps, float wd, float gscale, const int* __restrict__ step_ptr, int step) {
-  const int t = step_ptr ? *step_ptr : step;
-  const float bc1 = 1.f - powf(b1, (float)t), bc2 = 1.f - powf(b2, (float)t);
-  const float step_size = lr / bc1, rbc2 = rsqrtf(bc2);
-  // p -= lr * wd * p as the one fma the compiler contracted it to; a zero decay (frozen
-  // parameters: lr = 0) leaves p alone bit for bit, where -0 - 0 * -0 would give +0
-  const float decay = lr * wd;
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 pv = ((f32x4*)p)[i], gv = ((const f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
-    bf16x4 o;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float gg = gv[u] * gscale;
-      mv[u] = b1 * mv[u] + (1.f - b1) * gg;
-      vv[u] = b2 * vv[u] + (1.f - b2) * gg * gg;
-      pv[u] = decay == 0.f ? pv[u] : __builtin_fmaf(-decay, pv[u], pv[u]);
-      pv[u] -= step_size * mv[u] / (sqrtf(vv[u]) * rbc2 + eps);
-      o[u] = (short)tobf(pv[u]);
-    }
-    __builtin_nontemporal_store(pv, (f32x4*)p + i);
-    __builtin_nontemporal_store(mv, (f32x4*)m + i);
-    __builtin_nontemporal_store(vv, (f32x4*)v + i);
-    if (pb) ((bf16x4*)pb)[i] = o;
+template <bool SWZ, bool PF>
+static void attn_bwd_half_launch_t(int Bn, int S, int nh, const void* qkv, const void* o,
+                                   const void* dout, const float* lse, const float* kmask,
+                                   float scale, void* dqkv, float* dbias, hipStream_t s) {
+  static bool hattr = false;
+  if (!hattr) {
+    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_half_kernel<SWZ, PF>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, atb::LDS<SWZ>()));
+    hattr = true;
   }
+  hipLaunchKernelGGL((attn_bwd_half_kernel<SWZ, PF>), dim3(Bn * nh), dim3(512), atb::LDS<SWZ>(), s,
+                     S, nh, (const unsigned short*)qkv, (const unsigned short*)o,
+                     (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv, dbias);
+}
+static Knob g_attn_bwd_pf{"DTFX_ATTN_BWD_PF", 0};  // (tests set both forms)
+void attn_bwd_set_pf(int v) { g_attn_bwd_pf.set(v); }
+static bool attn_bwd_pf() { return g_attn_bwd_pf.get() == 1; }
+template <bool SWZ>
+static void attn_bwd_half_launch(int Bn, int S, int nh, const void* qkv, const void* o,
+                                 const void* dout, const float* lse, const float* kmask,
+                                 float scale, void* dqkv, float* dbias, hipStream_t s) {
+  if (attn_bwd_pf())
+    attn_bwd_half_launch_t<SWZ, true>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
+  else
+    attn_bwd_half_launch_t<SWZ, false>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
 }
 
-// The same AdamW with the weight gradients of some flat ranges ("segments") left as split-K
-// partial planes by their GEMMs (gemm_bf16_launch defer_reduce): the split planes are summed
-// here, in split order, instead of by a reduce pass that writes the gradient only for this
-// kernel to read it back.  Used when nothing sits between the weight gradient and the
-// optimizer (one GPU: no all-reduce).  Segment k (int64 x 5, sorted by start, disjoint):
-// {lo4, hi4 (float4 indices into the flat buffer), partial planes (f32 pointer), plane
-// stride in float4s, S}.  A lane finds its segment by binary search in LDS (<= 128 entries).
-constexpr int kAdamMaxSegs = 128;
-__global__ __launch_bounds__(256) void adam_mixed_segs_kernel(
-    long long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    float* __restrict__ v, unsigned short* __restrict__ pb, float lr, float b1, float b2,
-    float eps, float wd, float gscale, const int* __restrict__ step_ptr, int step,
-    const long long* __restrict__ segs, int nseg, long long base4) {
-  __shared__ long long s_lo[kAdamMaxSegs], s_hi[kAdamMaxSegs], s_pl[kAdamMaxSegs];
-  __shared__ const f32x4* s_w[kAdamMaxSegs];
-  __shared__ int s_S[kAdamMaxSegs];
-  // segment bounds are absolute float4 indices of the whole flat buffer; this launch covers
-  // [base4, base4 + n / 4) of it (a bucket's range)
-  for (int k = threadIdx.x; k < nseg; k += blockDim.x) {
-    s_lo[k] = segs[5 * k] - base4;
-    s_hi[k] = segs[5 * k + 1] - base4;
-    s_w[k] = (const f32x4*)segs[5 * k + 2];
-    s_pl[k] = segs[5 * k + 3];
-    s_S[k] = (int)segs[5 * k + 4];
+// Attention-backward kernel: -1 = from the environment, 0: attn_bwd_kernel<8>,
+// 1: attn_bwd_kernel<4>, 2: attn_bwd_half_kernel, 3: attn_bwd_persist_kernel, 4: the same on a
+// 3-block grid (tests run every variant in one process).
+static int g_attn_bwd_variant = -1;
+void attn_bwd_set_variant(int v) { g_attn_bwd_variant = v; }
+
+void attn_bwd_launch(int Bn, int S, int nh, const void* qkv, const void* o, const void* dout,
+                     const float* lse, const float* kmask, float scale, void* dqkv, float* dbias,
+                     hipStream_t s) {
+  check_attn(S, nh);
+  const size_t lds = 4 * at::QB + 2 * at::PB + at::SP * 4;
+  static bool attr = false;
+  if (!attr) {
+    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_kernel<4>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_kernel<8>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
   }
-  __syncthreads();
-  const int t = step_ptr ? *step_ptr : step;
-  const float bc1 = 1.f - powf(b1, (float)t), bc2 = 1.f - powf(b2, (float)t);
-  const float step_size = lr / bc1, rbc2 = rsqrtf(bc2);
-  // p -= lr * wd * p as the one fma the compiler contracted it to; a zero decay (frozen
-  // parameters: lr = 0) leaves p alone bit for bit, where -0 - 0 * -0 would give +0
-  const float decay = lr * wd;
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    // last segment with lo <= i
-    int lo = 0, hi = nseg - 1, k = -1;
-    while (lo <= hi) {
-      const int mid = (lo + hi) >> 1;
-      if (s_lo[mid] <= i) {
-        k = mid;
-        lo = mid + 1;
-      } else {
-        hi = mid - 1;
-      }
+  static const int nw = env_int("DTFX_ATTN_BWD_WAVES", 8) == 4 ? 4 : 8;
+  // The two-blocks-per-CU kernel (default; DTFX_ATTN_BWD_HALF=0: the 8-wave one).  Alone it is
+  // 14-18 % faster (BERT-base shape, batch 128: 56.9 vs 66.3 us).  Beside the weight-gradient
+  // GEMMs of a second stream it lost that (round 3: 7892 vs 7924 seq/s); with the one-GPU BERT
+  // step now issuing its weight gradients in order (train/bert_trainer.py) it gains: 7,903-7,919
+  // -> 8,034-8,055 seq/s interleaved (profiles/r4/bert/half_nows/).
+  static const bool half = env_int("DTFX_ATTN_BWD_HALF", 1) != 0;
+  // DTFX_ATTN_BWD_PERSIST=1: the persistent kernel (grid: DTFX_ATTN_BWD_BLOCKS, default one
+  // block per CU).  Measured slower: 84 us standalone vs 68 for the 8-wave per-pair kernel (128
+  // blocks: 144 us), BERT 7,922-7,947 vs 7,960-8,003 seq/s (profiles/r4/bert/attn_persist/):
+  // the pairs are not load-latency-bound but bound inside their compute phases (~11 us per
+  // pair per CU against ~1 us of MFMA work), which one wave per SIMD hides worse.
+  static const bool persist = env_int("DTFX_ATTN_BWD_PERSIST", 0) == 1;
+  const int var = g_attn_bwd_variant >= 0 ? g_attn_bwd_variant : persist ? 3 : half ? 2 : nw == 4 ? 1 : 0;
+  if (var == 3 || var == 4) {
+    // 4 waves: one per SIMD with up to 512 registers each -- the 8-wave form's 40 prefetch
+    // registers spilled
+    static bool pattr = false;
+    if (!pattr) {
+      DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_persist_kernel<4>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      pattr = true;
     }
-    f32x4 gv;
-    if (k >= 0 && i < s_hi[k]) {
-      const f32x4* w = s_w[k] + (i - s_lo[k]);
-      const long long pl = s_pl[k];
-      const int S = s_S[k];
-      // the planes four at a time, loads first (a plain loop waited out one round trip per
-      // plane: 14 for the attention-output weights), added in split order
-      gv = __builtin_nontemporal_load(w);
-      int q = 1;
-      for (; q + 3 < S; q += 4) {
-        const f32x4 a0 = __builtin_nontemporal_load(w + q * pl), a1 = __builtin_nontemporal_load(w + (q + 1) * pl),
-                    a2 = __builtin_nontemporal_load(w + (q + 2) * pl), a3 = __builtin_nontemporal_load(w + (q + 3) * pl);
-        gv += a0;
-        gv += a1;
-        gv += a2;
-        gv += a3;
-      }
-      if (q + 1 < S) {
-        const f32x4 a0 = __builtin_nontemporal_load(w + q * pl), a1 = __builtin_nontemporal_load(w + (q + 1) * pl);
-        gv += a0;
-        gv += a1;
-        q += 2;
-      }
-      if (q < S) gv += __builtin_nontemporal_load(w + q * pl);
-    } else {
-      gv = __builtin_nontemporal_load((const f32x4*)g + i);
-    }
-    f32x4 pv = __builtin_nontemporal_load((f32x4*)p + i), mv = __builtin_nontemporal_load((f32x4*)m + i),
-          vv = __builtin_nontemporal_load((f32x4*)v + i);
-    bf16x4 o;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float gg = gv[u] * gscale;
-      mv[u] = b1 * mv[u] + (1.f - b1) * gg;
-      vv[u] = b2 * vv[u] + (1.f - b2) * gg * gg;
-      pv[u] = decay == 0.f ? pv[u] : __builtin_fmaf(-decay, pv[u], pv[u]);
-      pv[u] -= step_size * mv[u] / (sqrtf(vv[u]) * rbc2 + eps);
-      o[u] = (short)tobf(pv[u]);
-    }
-    __builtin_nontemporal_store(pv, (f32x4*)p + i);
-    __builtin_nontemporal_store(mv, (f32x4*)m + i);
-    __builtin_nontemporal_store(vv, (f32x4*)v + i);
-    if (pb) ((bf16x4*)pb)[i] = o;
-  }
+    static const int blocks = [] {
+      const char* e = std::getenv("DTFX_ATTN_BWD_BLOCKS");
+      return e && std::atoi(e) > 0 ? std::atoi(e) : 256;
+    }();
+    const int np = Bn * nh, nb = var == 4 ? 3 : blocks;  // 4: a 3-block grid (tests: many pairs per block)
+    hipLaunchKernelGGL(attn_bwd_persist_kernel<4>, dim3(std::min(np, nb)), dim3(256), lds, s, S, nh,
+                       np, (const unsigned short*)qkv, (const unsigned short*)o,
+                       (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv, dbias);
+  } else if (var == 2) {
+    if (attn_swz())
+      attn_bwd_half_launch<true>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
+    else
+      attn_bwd_half_launch<false>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
+  } else if (var == 1)
+    hipLaunchKernelGGL(attn_bwd_kernel<4>, dim3(Bn * nh), dim3(256), lds, s, S, nh,
+                       (const unsigned short*)qkv, (const unsigned short*)o,
+                       (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv,
+                       dbias);
+  else
+    hipLaunchKernelGGL(attn_bwd_kernel<8>, dim3(Bn * nh), dim3(512), lds, s, S, nh,
+                       (const unsigned short*)qkv, (const unsigned short*)o,
+                       (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv,
+                       dbias);
+  DTFX_HIP_CHECK(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------
@@ -1856,327 +1921,161 @@ __global__ __launch_bounds__(256) void mlm_xent_regs_kernel(int C, const unsigne
   }
 }
 
-// dx = dy * act'(u), bf16 (gelu-tanh: act 1, relu: act 2); n % 8 == 0
-__global__ __launch_bounds__(256) void act_grad_bf16_kernel(long long n8, int act,
-                                                            const unsigned short* __restrict__ dy,
-                                                            const unsigned short* __restrict__ u,
-                                                            unsigned short* __restrict__ dx) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
-    float a[8], b[8];
-    unpack8(((const bf16x8*)dy)[i], a);
-    unpack8(((const bf16x8*)u)[i], b);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float x = b[k];
-      float d;
-      if (act == 1) {
-        const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-        const float th = tanhf(k0 * (x + k1 * x * x * x));
-        d = 0.5f * (1.f + th) + 0.5f * x * (1.f - th * th) * k0 * (1.f + 3.f * k1 * x * x);
-      } else {
-        d = x > 0.f ? 1.f : 0.f;
-      }
-      a[k] *= d;
-    }
-    __builtin_nontemporal_store(pack8(a), (bf16x8*)dx + (i));
-  }
-}
+static Knob g_xent_regs{"DTFX_XENT_REGS", 1};  // (tests set both forms)
+void xent_set_regs(int v) { g_xent_regs.set(v); }
 
-__global__ __launch_bounds__(256) void cast_f32_bf16_kernel(long long n, const float* __restrict__ x,
-                                                            unsigned short* __restrict__ y) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    y[i] = tobf(x[i]);
-}
-
-// ---------------------------------------------------------------------------
-// launchers
-// ---------------------------------------------------------------------------
-static void check_h(int H) {
-  if (H % 8 || H > 2048) throw std::runtime_error("transformer: H must be a multiple of 8 and <= 2048");
-}
-
-void layernorm_fwd_launch(int T, int H, const void* x, const float* gamma, const float* beta,
-                          float eps, void* y, float* mean, float* rstd, hipStream_t s) {
-  check_h(H);
-  if (T <= 0) return;
-  // rows per wave (DTFX_LN_FWD_ROWS=1: the one-row kernel, for A/B runs)
-  static const int rows = [] {
-    const char* e = getenv("DTFX_LN_FWD_ROWS");
-    return e ? atoi(e) : 4;
-  }();
-  const auto* xs = (const unsigned short*)x;
-  auto* ys = (unsigned short*)y;
-  const int nc = (H + 511) / 512;
-  if ((rows == 4 || rows == 2) && !(((uintptr_t)gamma | (uintptr_t)beta) & 15)) {  // (f32x4 gamma / beta)
-    const int per_block = 4 * rows;
-    const dim3 grid((T + per_block - 1) / per_block);
-#define DTFX_LNF(NC_, R_) \
-  hipLaunchKernelGGL((layernorm_fwd_rows_kernel<NC_, R_>), grid, dim3(256), 0, s, T, H, xs, gamma, beta, eps, ys, mean, rstd)
-    if (rows == 4) {
-      if (nc == 1) DTFX_LNF(1, 4); else if (nc == 2) DTFX_LNF(2, 4); else if (nc == 3) DTFX_LNF(3, 4); else DTFX_LNF(4, 4);
-    } else {
-      if (nc == 1) DTFX_LNF(1, 2); else if (nc == 2) DTFX_LNF(2, 2); else if (nc == 3) DTFX_LNF(3, 2); else DTFX_LNF(4, 2);
-    }
-#undef DTFX_LNF
-  } else {
-    hipLaunchKernelGGL(layernorm_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, T, H, xs, gamma, beta, eps,
-                       ys, mean, rstd);
-  }
-  DTFX_HIP_CHECK(hipGetLastError());
-}
-
-static int g_ln_slots = -1;  // -1: DTFX_LN_SLOTS (tests set both forms)
-void ln_bwd_set_slots(int v) { g_ln_slots = v; }
-static int g_ln_h768 = -1;  // -1: DTFX_LN_H768
-void ln_bwd_set_h768(int v) { g_ln_h768 = v; }
-
-void layernorm_bwd_launch(int T, int H, const void* dy, const void* x, const float* mean,
-                          const float* rstd, const float* gamma, const void* dres, void* dx,
-                          float* dgamma, float* dbeta, float* dxsum, hipStream_t s) {
-  check_h(H);
-  if (T <= 0) return;
-  // BERT 16384 rows: 256 blocks (measured 16: 54 us, 32: 35, 64: 31, 128: 38 -- atomics vs
-  // parallelism; with two rows in flight per wave 32: 33.9, 64: 26.5, 128: 29.8 us).  DTFX_LN_RPB overrides (sweeps).
-  static const int rpb_env = [] {
-    const char* e = getenv("DTFX_LN_RPB");
-    return e ? atoi(e) : 0;
-  }();
-  static const int slots_env = [] {
-    const char* e = getenv("DTFX_LN_SLOTS");
-    return e ? std::max(1, std::min(3, atoi(e))) : 2;
-  }();
-  // row slots per wave of the generic kernel: 2 (default) or 3
-  const int slots = g_ln_slots >= 0 ? std::max(1, std::min(3, g_ln_slots)) : slots_env;
-  static const int h768_env = [] {
-    const char* e = getenv("DTFX_LN_H768");
-    return e ? atoi(e) : 0;
-  }();
-  if (H == 768 && (g_ln_h768 >= 0 ? g_ln_h768 : h768_env) == 1 && !(((uintptr_t)gamma) & 15)) {
-    // 4 rows per wave at the BERT shape (512 blocks, two per CU)
-    const int rpb7 = rpb_env > 0 ? rpb_env : (T >= 8192 ? 32 : 8);
-    // one row slot per wave: the 16 resident waves per CU are the pipeline (two slots spill
-    // at the 128 VGPRs four waves per SIMD allow)
-    hipLaunchKernelGGL(layernorm_bwd_h768_kernel<1>, dim3((T + rpb7 - 1) / rpb7), dim3(512), 0, s,
-                         T, rpb7, (const unsigned short*)dy, (const unsigned short*)x, mean, rstd,
-                         gamma, (const unsigned short*)dres, (unsigned short*)dx, dgamma, dbeta, dxsum);
+void mlm_xent_launch(int N, int C, const void* logits, bool logits_bf16, int ldl, const int* labels,
+                     float scale, float* loss, float* correct, void* dl, int ldd, hipStream_t s) {
+  if (ldl % 4 || ldd % 4 || ldd < C || ldl < C)
+    throw std::runtime_error("mlm_xent: ldl/ldd must be multiples of 4 and >= C");
+  if (N <= 0) return;
+  const bool regs = g_xent_regs.get() == 1;
+  if (logits_bf16 && regs && ldl % 8 == 0 && ldd % 8 == 0 && ldd <= 256 * 8 * kXentChunks &&
+      !(((uintptr_t)logits | (uintptr_t)dl) & 15)) {
+    hipLaunchKernelGGL(mlm_xent_regs_kernel, dim3(N), dim3(256), 0, s, C,
+                       (const unsigned short*)logits, ldl, labels, scale, loss, correct,
+                       (unsigned short*)dl, ldd);
     DTFX_HIP_CHECK(hipGetLastError());
     return;
   }
-  const int rpb = rpb_env > 0 ? rpb_env : (T >= 8192 ? 64 : 16);
-  const int nc = (H / 8 + 63) / 64;
-#define DTFX_LNB(NC_, NS_)                                                                      \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<NC_, NS_>), dim3((T + rpb - 1) / rpb), dim3(NC_ <= 2 ? 512 : 256), 0, s, T, H, \
-                     rpb, (const unsigned short*)dy, (const unsigned short*)x, mean, rstd, gamma,  \
-                     (const unsigned short*)dres, (unsigned short*)dx, dgamma, dbeta, dxsum)
-  if (nc == 1 && slots >= 3) DTFX_LNB(1, 3);
-  else if (nc == 2 && slots >= 3) DTFX_LNB(2, 3);
-  else if (nc == 1) DTFX_LNB(1, 2);
-  else if (nc == 2) DTFX_LNB(2, 2);
-  else if (nc == 3) DTFX_LNB(3, 2);
-  else DTFX_LNB(4, 2);
-#undef DTFX_LNB
-  DTFX_HIP_CHECK(hipGetLastError());
-}
-
-void embed_ln_fwd_launch(int T, int S, int H, const int* ids, const int* tt, const void* word,
-                         const void* pos, const void* type, const float* gamma, const float* beta,
-                         float eps, void* xsum, void* y, float* mean, float* rstd, hipStream_t s) {
-  check_h(H);
-  if (T <= 0) return;
-  hipLaunchKernelGGL(embed_ln_fwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, T, S, H, ids, tt,
-                     (const unsigned short*)word, (const unsigned short*)pos,
-                     (const unsigned short*)type, gamma, beta, eps, (unsigned short*)xsum,
-                     (unsigned short*)y, mean, rstd);
-  DTFX_HIP_CHECK(hipGetLastError());
-}
-
-void embed_bwd_launch(int Bn, int S, int H, const int* ids, const int* tt, const void* dx,
-                      float* dword, float* dpos, float* dtype_, hipStream_t s) {
-  check_h(H);
-  const int T = Bn * S;
-  if (T <= 0) return;
-  hipLaunchKernelGGL(embed_word_bwd_kernel, dim3((T + 3) / 4), dim3(256), 0, s, T, H, ids,
-                     (const unsigned short*)dx, dword);
-  DTFX_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(embed_pos_type_bwd_kernel, dim3(S), dim3(1024), 0, s, Bn, S, H, tt,
-                     (const unsigned short*)dx, dpos, dtype_);
-  DTFX_HIP_CHECK(hipGetLastError());
-}
-
-static void check_attn(int S, int nh) {
-  if (S <= 0 || S > at::SP) throw std::runtime_error("attention: fused kernel needs 0 < S <= 128");
-  if (nh <= 0) throw std::runtime_error("attention: nh must be positive");
-}
-
-// Swizzled attention images (opt-in, measured slower: see attn_fwd_kernel): -1 = from the
-// environment (DTFX_ATTN_SWZ=1), 0 / 1 forced (tests run both in one process).
-static int g_attn_swz = -1;
-void attn_set_swizzle(int v) { g_attn_swz = v; }
-static bool attn_swz() {
-  static const bool env = [] {
-    const char* e = std::getenv("DTFX_ATTN_SWZ");
-    return e && std::atoi(e) == 1;
-  }();
-  return g_attn_swz >= 0 ? g_attn_swz == 1 : env;
-}
-
-template <bool SWZ>
-static void attn_fwd_launch_t(int Bn, int S, int nh, const void* qkv, void* out, float* lse,
-                              const float* kmask, float scale, hipStream_t s) {
-  const size_t lds = 2 * (size_t)at::SP * at::img_pitch<SWZ>() + at::PB;
-  static bool attr = false;
-  if (!attr) {
-    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_kernel<SWZ>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL(attn_fwd_kernel<SWZ>, dim3(Bn * nh), dim3(256), lds, s, S, nh,
-                     (const unsigned short*)qkv, (unsigned short*)out, lse, kmask, scale);
-}
-
-// Attention forward: -1 = from DTFX_ATTN_FWD (default 1), 1: attn_fwd_rp_kernel (P in
-// registers), 0: attn_fwd_kernel (P through LDS; DTFX_ATTN_SWZ picks its swizzled variant)
-static int g_attn_fwd = -1;
-void attn_fwd_set_variant(int v) { g_attn_fwd = v; }
-static bool attn_fwd_rp() {
-  if (g_attn_fwd < 0) {
-    const char* e = getenv("DTFX_ATTN_FWD");
-    g_attn_fwd = e && atoi(e) == 0 ? 0 : 1;
-  }
-  return g_attn_fwd == 1;
-}
-
-void attn_fwd_launch(int Bn, int S, int nh, const void* qkv, void* out, float* lse,
-                     const float* kmask, float scale, hipStream_t s) {
-  check_attn(S, nh);
-  if (attn_fwd_rp()) {
-    constexpr size_t lds = 2 * (size_t)at::QB + (size_t)at::SP * 4;
-    static bool attr = false;
-    if (!attr) {
-      DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_fwd_rp_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr = true;
-    }
-    hipLaunchKernelGGL(attn_fwd_rp_kernel, dim3(Bn * nh), dim3(256), lds, s, S, nh,
-                       (const unsigned short*)qkv, (unsigned short*)out, lse, kmask, scale);
-  } else if (attn_swz()) {
-    attn_fwd_launch_t<true>(Bn, S, nh, qkv, out, lse, kmask, scale, s);
-  } else {
-    attn_fwd_launch_t<false>(Bn, S, nh, qkv, out, lse, kmask, scale, s);
-  }
-  DTFX_HIP_CHECK(hipGetLastError());
-}
-
-template <bool SWZ, bool PF>
-static void attn_bwd_half_launch_t(int Bn, int S, int nh, const void* qkv, const void* o,
-                                   const void* dout, const float* lse, const float* kmask,
-                                   float scale, void* dqkv, float* dbias, hipStream_t s) {
-  static bool hattr = false;
-  if (!hattr) {
-    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_half_kernel<SWZ, PF>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, atb::LDS<SWZ>()));
-    hattr = true;
-  }
-  hipLaunchKernelGGL((attn_bwd_half_kernel<SWZ, PF>), dim3(Bn * nh), dim3(512), atb::LDS<SWZ>(), s,
-                     S, nh, (const unsigned short*)qkv, (const unsigned short*)o,
-                     (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv, dbias);
-}
-static int g_attn_bwd_pf = -1;  // -1: DTFX_ATTN_BWD_PF (tests set both forms)
-void attn_bwd_set_pf(int v) { g_attn_bwd_pf = v; }
-static bool attn_bwd_pf() {
-  static const bool env = [] {
-    const char* e = std::getenv("DTFX_ATTN_BWD_PF");
-    return e && std::atoi(e) == 1;
-  }();
-  return g_attn_bwd_pf >= 0 ? g_attn_bwd_pf == 1 : env;
-}
-template <bool SWZ>
-static void attn_bwd_half_launch(int Bn, int S, int nh, const void* qkv, const void* o,
-                                 const void* dout, const float* lse, const float* kmask,
-                                 float scale, void* dqkv, float* dbias, hipStream_t s) {
-  if (attn_bwd_pf())
-    attn_bwd_half_launch_t<SWZ, true>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
+  if (logits_bf16)
+    hipLaunchKernelGGL(mlm_xent_kernel<unsigned short>, dim3(N), dim3(256), 0, s, C,
+                       (const unsigned short*)logits, ldl, labels, scale, loss, correct,
+                       (unsigned short*)dl, ldd);
   else
-    attn_bwd_half_launch_t<SWZ, false>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
+    hipLaunchKernelGGL(mlm_xent_kernel<float>, dim3(N), dim3(256), 0, s, C, (const float*)logits, ldl,
+                       labels, scale, loss, correct, (unsigned short*)dl, ldd);
+  DTFX_HIP_CHECK(hipGetLastError());
 }
 
-// Attention-backward kernel: -1 = from the environment, 0: attn_bwd_kernel<8>,
-// 1: attn_bwd_kernel<4>, 2: attn_bwd_half_kernel, 3: attn_bwd_persist_kernel, 4: the same on a
-// 3-block grid (tests run every variant in one process).
-static int g_attn_bwd_variant = -1;
-void attn_bwd_set_variant(int v) { g_attn_bwd_variant = v; }
-
-void attn_bwd_launch(int Bn, int S, int nh, const void* qkv, const void* o, const void* dout,
-                     const float* lse, const float* kmask, float scale, void* dqkv, float* dbias,
-                     hipStream_t s) {
-  check_attn(S, nh);
-  const size_t lds = 4 * at::QB + 2 * at::PB + at::SP * 4;
-  static bool attr = false;
-  if (!attr) {
-    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_kernel<4>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_kernel<8>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  static const int nw = [] {
-    const char* e = std::getenv("DTFX_ATTN_BWD_WAVES");
-    return e && std::atoi(e) == 4 ? 4 : 8;
-  }();
-  // The two-blocks-per-CU kernel (default; DTFX_ATTN_BWD_HALF=0: the 8-wave one).  Alone it is
-  // 14-18 % faster (BERT-base shape, batch 128: 56.9 vs 66.3 us).  Beside the weight-gradient
-  // GEMMs of a second stream it lost that (round 3: 7892 vs 7924 seq/s); with the one-GPU BERT
-  // step now issuing its weight gradients in order (train/bert_trainer.py) it gains: 7,903-7,919
-  // -> 8,034-8,055 seq/s interleaved (profiles/r4/bert/half_nows/).
-  static const bool half = [] {
-    const char* e = std::getenv("DTFX_ATTN_BWD_HALF");
-    return !(e && std::atoi(e) == 0);
-  }();
-  // DTFX_ATTN_BWD_PERSIST=1: the persistent kernel (grid: DTFX_ATTN_BWD_BLOCKS, default one
-  // block per CU).  Measured slower: 84 us standalone vs 68 for the 8-wave per-pair kernel (128
-  // blocks: 144 us), BERT 7,922-7,947 vs 7,960-8,003 seq/s (profiles/r4/bert/attn_persist/):
-  // the pairs are not load-latency-bound but bound inside their compute phases (~11 us per
-  // pair per CU against ~1 us of MFMA work), which one wave per SIMD hides worse.
-  static const bool persist = [] {
-    const char* e = std::getenv("DTFX_ATTN_BWD_PERSIST");
-    return e && std::atoi(e) == 1;
-  }();
-  const int var = g_attn_bwd_variant >= 0 ? g_attn_bwd_variant : persist ? 3 : half ? 2 : nw == 4 ? 1 : 0;
-  if (var == 3 || var == 4) {
-    // 4 waves: one per SIMD with up to 512 registers each -- the 8-wave form's 40 prefetch
-    // registers spilled
-    static bool pattr = false;
-    if (!pattr) {
-      DTFX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_bwd_persist_kernel<4>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      pattr = true;
+// ---------------------------------------------------------------------------
+// Mixed-precision Adam(W): f32 master p, grad g, moments m, v; writes the bf16
+// working copy pb used by the GEMMs.  Grad scale folds the 1/world average.  p, m, v are
+// streamed (non-temporal: next read a whole step later), the bf16 copy is stored normally
+// (BERT-base +1.0 % together with the GEMMs' non-temporal f32 / split-K stores,
+// profiles/r5/gemm_nt/nt2/).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void adam_mixed_kernel(
+    long long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, unsigned short* __restrict__ pb, float lr, float b1, float b2,
+    float eps, float wd, float gscale, const int* __restrict__ step_ptr, int step) {
+  const int t = step_ptr ? *step_ptr : step;
+  const float bc1 = 1.f - powf(b1, (float)t), bc2 = 1.f - powf(b2, (float)t);
+  const float step_size = lr / bc1, rbc2 = rsqrtf(bc2);
+  // p -= lr * wd * p as the one fma the compiler contracted it to; a zero decay (frozen
+  // parameters: lr = 0) leaves p alone bit for bit, where -0 - 0 * -0 would give +0
+  const float decay = lr * wd;
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 pv = ((f32x4*)p)[i], gv = ((const f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+    bf16x4 o;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float gg = gv[u] * gscale;
+      mv[u] = b1 * mv[u] + (1.f - b1) * gg;
+      vv[u] = b2 * vv[u] + (1.f - b2) * gg * gg;
+      pv[u] = decay == 0.f ? pv[u] : __builtin_fmaf(-decay, pv[u], pv[u]);
+      pv[u] -= step_size * mv[u] / (sqrtf(vv[u]) * rbc2 + eps);
+      o[u] = (short)tobf(pv[u]);
     }
-    static const int blocks = [] {
-      const char* e = std::getenv("DTFX_ATTN_BWD_BLOCKS");
-      return e && std::atoi(e) > 0 ? std::atoi(e) : 256;
-    }();
-    const int np = Bn * nh, nb = var == 4 ? 3 : blocks;  // 4: a 3-block grid (tests: many pairs per block)
-    hipLaunchKernelGGL(attn_bwd_persist_kernel<4>, dim3(std::min(np, nb)), dim3(256), lds, s, S, nh,
-                       np, (const unsigned short*)qkv, (const unsigned short*)o,
-                       (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv, dbias);
-  } else if (var == 2) {
-    if (attn_swz())
-      attn_bwd_half_launch<true>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
-    else
-      attn_bwd_half_launch<false>(Bn, S, nh, qkv, o, dout, lse, kmask, scale, dqkv, dbias, s);
-  } else if (var == 1)
-    hipLaunchKernelGGL(attn_bwd_kernel<4>, dim3(Bn * nh), dim3(256), lds, s, S, nh,
-                       (const unsigned short*)qkv, (const unsigned short*)o,
-                       (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv,
-                       dbias);
-  else
-    hipLaunchKernelGGL(attn_bwd_kernel<8>, dim3(Bn * nh), dim3(512), lds, s, S, nh,
-                       (const unsigned short*)qkv, (const unsigned short*)o,
-                       (const unsigned short*)dout, lse, kmask, scale, (unsigned short*)dqkv,
-                       dbias);
-  DTFX_HIP_CHECK(hipGetLastError());
+    __builtin_nontemporal_store(pv, (f32x4*)p + i);
+    __builtin_nontemporal_store(mv, (f32x4*)m + i);
+    __builtin_nontemporal_store(vv, (f32x4*)v + i);
+    if (pb) ((bf16x4*)pb)[i] = o;
+  }
+}
+
+// The same AdamW with the weight gradients of some flat ranges ("segments") left as split-K
+// partial planes by their GEMMs (gemm_bf16_launch defer_reduce): the split planes are summed
+// here, in split order, instead of by a reduce pass that writes the gradient only for this
+// kernel to read it back.  Used when nothing sits between the weight gradient and the
+// optimizer (one GPU: no all-reduce).  Segment k (int64 x 5, sorted by start, disjoint):
+// {lo4, hi4 (float4 indices into the flat buffer), partial planes (f32 pointer), plane
+// stride in float4s, S}.  A lane finds its segment by binary search in LDS (<= 128 entries).
+constexpr int kAdamMaxSegs = 128;
+__global__ __launch_bounds__(256) void adam_mixed_segs_kernel(
+    long long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, unsigned short* __restrict__ pb, float lr, float b1, float b2,
+    float eps, float wd, float gscale, const int* __restrict__ step_ptr, int step,
+    const long long* __restrict__ segs, int nseg, long long base4) {
+  __shared__ long long s_lo[kAdamMaxSegs], s_hi[kAdamMaxSegs], s_pl[kAdamMaxSegs];
+  __shared__ const f32x4* s_w[kAdamMaxSegs];
+  __shared__ int s_S[kAdamMaxSegs];
+  // segment bounds are absolute float4 indices of the whole flat buffer; this launch covers
+  // [base4, base4 + n / 4) of it (a bucket's range)
+  for (int k = threadIdx.x; k < nseg; k += blockDim.x) {
+    s_lo[k] = segs[5 * k] - base4;
+    s_hi[k] = segs[5 * k + 1] - base4;
+    s_w[k] = (const f32x4*)segs[5 * k + 2];
+    s_pl[k] = segs[5 * k + 3];
+    s_S[k] = (int)segs[5 * k + 4];
+  }
+  __syncthreads();
+  const int t = step_ptr ? *step_ptr : step;
+  const float bc1 = 1.f - powf(b1, (float)t), bc2 = 1.f - powf(b2, (float)t);
+  const float step_size = lr / bc1, rbc2 = rsqrtf(bc2);
+  // p -= lr * wd * p as the one fma the compiler contracted it to; a zero decay (frozen
+  // parameters: lr = 0) leaves p alone bit for bit, where -0 - 0 * -0 would give +0
+  const float decay = lr * wd;
+  const long long n4 = n >> 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    // last segment with lo <= i
+    int lo = 0, hi = nseg - 1, k = -1;
+    while (lo <= hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_lo[mid] <= i) {
+        k = mid;
+        lo = mid + 1;
+      } else {
+        hi = mid - 1;
+      }
+    }
+    f32x4 gv;
+    if (k >= 0 && i < s_hi[k]) {
+      const f32x4* w = s_w[k] + (i - s_lo[k]);
+      const long long pl = s_pl[k];
+      const int S = s_S[k];
+      // the planes four at a time, loads first (a plain loop waited out one round trip per
+      // plane: 14 for the attention-output weights), added in split order
+      gv = __builtin_nontemporal_load(w);
+      int q = 1;
+      for (; q + 3 < S; q += 4) {
+        const f32x4 a0 = __builtin_nontemporal_load(w + q * pl), a1 = __builtin_nontemporal_load(w + (q + 1) * pl),
+                    a2 = __builtin_nontemporal_load(w + (q + 2) * pl), a3 = __builtin_nontemporal_load(w + (q + 3) * pl);
+        gv += a0;
+        gv += a1;
+        gv += a2;
+        gv += a3;
+      }
+      if (q + 1 < S) {
+        const f32x4 a0 = __builtin_nontemporal_load(w + q * pl), a1 = __builtin_nontemporal_load(w + (q + 1) * pl);
+        gv += a0;
+        gv += a1;
+        q += 2;
+      }
+      if (q < S) gv += __builtin_nontemporal_load(w + q * pl);
+    } else {
+      gv = __builtin_nontemporal_load((const f32x4*)g + i);
+    }
+    f32x4 pv = __builtin_nontemporal_load((f32x4*)p + i), mv = __builtin_nontemporal_load((f32x4*)m + i),
+          vv = __builtin_nontemporal_load((f32x4*)v + i);
+    bf16x4 o;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float gg = gv[u] * gscale;
+      mv[u] = b1 * mv[u] + (1.f - b1) * gg;
+      vv[u] = b2 * vv[u] + (1.f - b2) * gg * gg;
+      pv[u] = decay == 0.f ? pv[u] : __builtin_fmaf(-decay, pv[u], pv[u]);
+      pv[u] -= step_size * mv[u] / (sqrtf(vv[u]) * rbc2 + eps);
+      o[u] = (short)tobf(pv[u]);
+    }
+    __builtin_nontemporal_store(pv, (f32x4*)p + i);
+    __builtin_nontemporal_store(mv, (f32x4*)m + i);
+    __builtin_nontemporal_store(vv, (f32x4*)v + i);
+    if (pb) ((bf16x4*)pb)[i] = o;
+  }
 }
 
 void adam_mixed_launch(long long n, float* p, const float* g, float* m, float* v, void* pb,
@@ -2208,35 +2107,31 @@ void adam_mixed_launch(long long n, float* p, const float* g, float* m, float* v
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
-static int g_xent_regs = -1;  // -1: DTFX_XENT_REGS (tests set both forms)
-void xent_set_regs(int v) { g_xent_regs = v; }
-
-void mlm_xent_launch(int N, int C, const void* logits, bool logits_bf16, int ldl, const int* labels,
-                     float scale, float* loss, float* correct, void* dl, int ldd, hipStream_t s) {
-  if (ldl % 4 || ldd % 4 || ldd < C || ldl < C)
-    throw std::runtime_error("mlm_xent: ldl/ldd must be multiples of 4 and >= C");
-  if (N <= 0) return;
-  static const int regs_env = [] {
-    const char* e = getenv("DTFX_XENT_REGS");
-    return e ? atoi(e) : 1;
-  }();
-  const bool regs = (g_xent_regs >= 0 ? g_xent_regs : regs_env) == 1;
-  if (logits_bf16 && regs && ldl % 8 == 0 && ldd % 8 == 0 && ldd <= 256 * 8 * kXentChunks &&
-      !(((uintptr_t)logits | (uintptr_t)dl) & 15)) {
-    hipLaunchKernelGGL(mlm_xent_regs_kernel, dim3(N), dim3(256), 0, s, C,
-                       (const unsigned short*)logits, ldl, labels, scale, loss, correct,
-                       (unsigned short*)dl, ldd);
-    DTFX_HIP_CHECK(hipGetLastError());
-    return;
+// dx = dy * act'(u), bf16 (gelu-tanh: act 1, relu: act 2); n % 8 == 0
+__global__ __launch_bounds__(256) void act_grad_bf16_kernel(long long n8, int act,
+                                                            const unsigned short* __restrict__ dy,
+                                                            const unsigned short* __restrict__ u,
+                                                            unsigned short* __restrict__ dx) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+    float a[8], b[8];
+    unpack8(((const bf16x8*)dy)[i], a);
+    unpack8(((const bf16x8*)u)[i], b);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float x = b[k];
+      float d;
+      if (act == 1) {
+        const float k0 = 0.7978845608028654f, k1 = 0.044715f;
+        const float th = tanhf(k0 * (x + k1 * x * x * x));
+        d = 0.5f * (1.f + th) + 0.5f * x * (1.f - th * th) * k0 * (1.f + 3.f * k1 * x * x);
+      } else {
+        d = x > 0.f ? 1.f : 0.f;
+      }
+      a[k] *= d;
+    }
+    __builtin_nontemporal_store(pack8(a), (bf16x8*)dx + (i));
   }
-  if (logits_bf16)
-    hipLaunchKernelGGL(mlm_xent_kernel<unsigned short>, dim3(N), dim3(256), 0, s, C,
-                       (const unsigned short*)logits, ldl, labels, scale, loss, correct,
-                       (unsigned short*)dl, ldd);
-  else
-    hipLaunchKernelGGL(mlm_xent_kernel<float>, dim3(N), dim3(256), 0, s, C, (const float*)logits, ldl,
-                       labels, scale, loss, correct, (unsigned short*)dl, ldd);
-  DTFX_HIP_CHECK(hipGetLastError());
 }
 
 void act_grad_bf16_launch(long long n, int act, const void* dy, const void* u, void* dx,
@@ -2247,6 +2142,22 @@ void act_grad_bf16_launch(long long n, int act, const void* dy, const void* u, v
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(act_grad_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n / 8, act,
                      (const unsigned short*)dy, (const unsigned short*)u, (unsigned short*)dx);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+__global__ __launch_bounds__(256) void cast_f32_bf16_kernel(long long n, const float* __restrict__ x,
+                                                            unsigned short* __restrict__ y) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    y[i] = tobf(x[i]);
+}
+
+void cast_f32_bf16_launch(long long n, const float* x, void* y, hipStream_t s) {
+  if (n <= 0) return;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, x,
+                     (unsigned short*)y);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
@@ -2276,15 +2187,6 @@ void zero_ranges_launch(const long long* tab, int n, long long total, hipStream_
   long long blocks = (total + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, n, total);
-  DTFX_HIP_CHECK(hipGetLastError());
-}
-
-void cast_f32_bf16_launch(long long n, const float* x, void* y, hipStream_t s) {
-  if (n <= 0) return;
-  long long blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n, x,
-                     (unsigned short*)y);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

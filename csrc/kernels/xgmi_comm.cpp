@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "knob.h"
 #include "mlp_step_api.h"
 #include "xgmi.h"
 
@@ -177,8 +178,8 @@ class XgmiAllReduce {
     xg.epochs = mlp_epochs_;
     xg.err = err_;
     xg.ticks = (long long)(timeout_s * 1e8);
-    const char* sp = getenv("DTFX_XG_SPLIT");
-    xg.split = sp ? atoi(sp) : 51;
+    static const int split = env_int("DTFX_XG_SPLIT", 51);
+    xg.split = split;
     return xg;
   }
 
