@@ -67,6 +67,22 @@ PYBIND11_MODULE(_hip, m) {
                           P<const int>(lab), P<float>(ws), B, S(s), P<unsigned long long>(tr));
   }, py::arg("p_old"), py::arg("grad"), py::arg("lr"), py::arg("p_new"), py::arg("labels"),
      py::arg("ws"), py::arg("B"), py::arg("stream"), py::arg("trace") = 0);
+  // Hidden-layer dropout (ops/dropout.py): the heads' DROP forms.  ctr: the device global_step
+  // counter; k0 / k1: the seed's words; thr, scale: dropout.threshold(rate); rank: the stream.
+  m.def("mlp_head_drop", [](uintptr_t p_old, uintptr_t grad, float lr, uintptr_t p_new,
+                            uintptr_t lab, uintptr_t ws, int B, uintptr_t s, uintptr_t ctr,
+                            unsigned k0, unsigned k1, unsigned thr, unsigned rank, float scale) {
+    const dtfx::MlpDrop d{P<const int>(ctr), k0, k1, thr, rank, scale};
+    dtfx::mlp_head_launch(P<const float>(p_old), P<const float>(grad), lr, P<float>(p_new),
+                          P<const int>(lab), P<float>(ws), B, S(s), nullptr, &d);
+  }, "mlp_head with inverted dropout on the hidden activation (mask: Philox of seed, *ctr, "
+     "rank, row, unit)");
+  m.def("mlp_lean_head_drop", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s,
+                                 uintptr_t ctr, unsigned k0, unsigned k1, unsigned thr,
+                                 unsigned rank, float scale) {
+    const dtfx::MlpDrop d{P<const int>(ctr), k0, k1, thr, rank, scale};
+    dtfx::mlp_lean_head_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s), &d);
+  }, "mlp_lean_head with inverted dropout on the hidden activation");
   m.def("mlp_wgrad", [](uintptr_t p, float lr, uintptr_t grad, uintptr_t x, uintptr_t ws,
                         uintptr_t ctr, uintptr_t stats, int ring, int B, uintptr_t s,
                         uintptr_t tr) {
@@ -169,6 +185,13 @@ PYBIND11_MODULE(_hip, m) {
     int* ctr;
     float* stats;
     int ring, B;
+    dtfx::MlpDrop drop{};  // set_drop: every head of the loop drops (ctr: the plan's)
+    bool has_drop = false;
+    const dtfx::MlpDrop* dropp() const { return has_drop ? &drop : nullptr; }
+    void set_drop(unsigned k0, unsigned k1, unsigned thr, unsigned rank, float scale) {
+      drop = dtfx::MlpDrop{ctr, k0, k1, thr, rank, scale};
+      has_drop = true;
+    }
   };
   static const auto bound = [](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
                                uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B) {
@@ -181,8 +204,11 @@ PYBIND11_MODULE(_hip, m) {
                      int flush, uintptr_t s) {
         py::gil_scoped_release nogil;
         dtfx::mlp_run_pipelined_launch(p.p0, p.p1, cur, pending, lr, p.x, p.labels, p.nbatches,
-                                       pos, n, p.ws, p.ctr, p.stats, p.ring, p.B, S(s), flush);
-      }, "(cur, pending, lr, pos, n, flush, stream): mlp_run_pipelined with the bound buffers");
+                                       pos, n, p.ws, p.ctr, p.stats, p.ring, p.B, S(s), flush,
+                                       p.dropp());
+      }, "(cur, pending, lr, pos, n, flush, stream): mlp_run_pipelined with the bound buffers")
+      .def("set_drop", &MlpRunPlan::set_drop,
+           "(k0, k1, thr, rank, scale): hidden-layer dropout in every head of the loop");
   m.def("mlp_apply", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev, uintptr_t ws,
                         uintptr_t ctr, uintptr_t stats, int ring, int B, uintptr_t s) {
     dtfx::mlp_apply_launch(P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev),
@@ -271,9 +297,12 @@ PYBIND11_MODULE(_hip, m) {
         py::gil_scoped_release nogil;
         dtfx::mlp_run_pipelined_opt_launch(p.p0, p.p1, cur, pending, lr, p.x, p.labels,
                                            p.nbatches, pos, n, p.ws, p.ctr, p.stats, p.ring, p.B,
-                                           S(s), flush, p.opt);
+                                           S(s), flush, p.opt, p.dropp());
       }, "(cur, pending, lr, pos, n, flush, stream): the C++ host loop of the two-launch step "
-         "with momentum / adam over the bound buffers (MlpRunPlan's call)");
+         "with momentum / adam over the bound buffers (MlpRunPlan's call)")
+      .def("set_drop", [](MlpRunOptPlan& p, unsigned k0, unsigned k1, unsigned thr, unsigned rank,
+                          float scale) { p.set_drop(k0, k1, thr, rank, scale); },
+           "(k0, k1, thr, rank, scale): hidden-layer dropout in every head of the loop");
   m.def("mlp_persistent_ll_words", &dtfx::mlp_persistent_ll_words);
   m.def("mlp_persistent_blocks", &dtfx::mlp_persistent_blocks);
   m.def("mlp_persistent_trace_steps", &dtfx::mlp_persistent_trace_steps);

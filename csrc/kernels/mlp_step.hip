@@ -185,14 +185,35 @@ void mlp_fwd_launch(const float* p_old, const float* grad, float lr, float* p_ne
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
+// Dropout (MlpDrop, mlp_step_api.h): the head's DROP instantiations.  thr in [1, 2^24] (ops/
+// dropout.py: threshold()); the step word is read from drop->ctr by the kernel.
+static void check_drop(const MlpDrop& d, const char* who) {
+  const char* bad = nullptr;
+  if (!d.ctr) bad = ": dropout needs the global_step counter";
+  else if (d.thr < 1u || d.thr > (1u << 24)) bad = ": dropout threshold must be in [1, 2^24]";
+  if (bad) throw std::runtime_error(std::string(who) + bad);
+}
+
 void mlp_head_launch(const float* p_old, const float* grad, float lr, float* p_new,
                      const int* labels, float* ws, int B, hipStream_t stream,
-                     unsigned long long* tr) {
+                     unsigned long long* tr, const MlpDrop* drop) {
   using namespace mlp;
   check_b(B);
   const Bufs w = make_bufs(ws, B);
   if (grad && (!p_new || p_new == p_old))
     throw std::runtime_error("mlp_head: apply needs ping-pong p_new");
+  if (drop) {
+    check_drop(*drop, "mlp_head");
+    if (tr) throw std::runtime_error("mlp_head: the trace launch has no dropout variant");
+    with_flag(grad != nullptr, [&](auto APPLY) {
+      hipLaunchKernelGGL((mlp_head_drop_kernel<APPLY()>), dim3(B), dim3(64), 0, stream, p_old,
+                         APPLY() ? grad : p_old, APPLY() ? lr : 0.f, APPLY() ? p_new : nullptr,
+                         labels, w, B, drop->ctr, drop->k0, drop->k1, drop->thr, drop->stream,
+                         drop->scale);
+    });
+    DTFX_HIP_CHECK(hipGetLastError());
+    return;
+  }
   auto launch = [&](auto APPLY, auto TRACE) {  // (no apply: grad = p_old, lr = 0, no p_new)
     hipLaunchKernelGGL((mlp_head_kernel<APPLY(), TRACE()>), dim3(B), dim3(64), 0, stream, p_old,
                        APPLY() ? grad : p_old, APPLY() ? lr : 0.f, APPLY() ? p_new : nullptr,
@@ -322,11 +343,16 @@ static void lean_first_launch(const float* p_old, float* p_new, float lr, const 
 }
 
 static void lean_head_launch(const float* p, const int* labels, float* ws, int B,
-                             hipStream_t stream) {
+                             hipStream_t stream, const MlpDrop* drop = nullptr) {
   using namespace mlp;
   with_ngt(B, [&](auto NGT) {
-    hipLaunchKernelGGL((mlp_lean_head_kernel<NGT()>), dim3(B), dim3(64), 0, stream, p, labels, ws,
-                       B);
+    if (drop)
+      hipLaunchKernelGGL((mlp_lean_head_drop_kernel<NGT()>), dim3(B), dim3(64), 0, stream, p,
+                         labels, ws, B, drop->ctr, drop->k0, drop->k1, drop->thr, drop->stream,
+                         drop->scale);
+    else
+      hipLaunchKernelGGL((mlp_lean_head_kernel<NGT()>), dim3(B), dim3(64), 0, stream, p, labels,
+                         ws, B);
   });
 }
 
@@ -372,11 +398,16 @@ void mlp_lean_fwdapply_launch(const float* p_old, float* p_new, float lr, const 
 
 // Its head (row-major factors out); DTFX_MLP_KS=14: mlp_head2_launch.
 void mlp_lean_head_launch(const float* p, const int* labels, float* ws, int B,
-                          hipStream_t stream) {
+                          hipStream_t stream, const MlpDrop* drop) {
+  if (drop) {
+    check_drop(*drop, "mlp_lean_head");
+    if (mlp_single_ks() != mlp::KS3)
+      throw std::runtime_error("mlp_lean_head: DTFX_MLP_KS=14 has no dropout variant");
+  }
   if (mlp_single_ks() != mlp::KS3) return mlp_head2_launch(p, labels, ws, B, stream, mlp::KS2);
   check_b(B);
   if (!p || !labels || !ws) throw std::runtime_error("mlp_lean_head: null buffer");
-  lean_head_launch(p, labels, ws, B, stream);
+  lean_head_launch(p, labels, ws, B, stream, drop);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
@@ -689,9 +720,17 @@ static void run_pipelined(float* p0, float* p1, int cur, int pending, const floa
 void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float lr,
                               const float* x, const int* labels, int nbatches, int pos, int n,
                               float* ws, int* ctr, float* stats, int stats_ring, int B,
-                              hipStream_t stream, int flush) {
+                              hipStream_t stream, int flush, const MlpDrop* drop) {
   using namespace mlp;
   check_b(B);
+  if (drop) {
+    check_drop(*drop, "mlp_run_pipelined");
+    if (mlp_single_ks() != KS3)
+      throw std::runtime_error("mlp_run_pipelined: DTFX_MLP_KS=14 has no dropout variant");
+    if (flush && mlp_flush_fused())
+      throw std::runtime_error(
+          "mlp_run_pipelined: the fused flush (DTFX_MLP_FLUSH_FUSED) has no dropout variant");
+  }
   if (!p0 || !p1 || p0 == p1 || !x || !labels || !ctr || nbatches < 1 || pos < 0 ||
       pos >= nbatches || n < 0)
     throw std::runtime_error("mlp_run_pipelined: bad buffers / position / count");
@@ -707,7 +746,7 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
       if constexpr (KSV() == KS3) {
         lean_first_launch<true>(po, pn, pend ? lr : 0.f, xprev, xcur, ws, ctr, stats, stats_ring, B,
                                 pend, stream);
-        lean_head_launch(pn, lab, ws, B, stream);
+        lean_head_launch(pn, lab, ws, B, stream, drop);
       } else {
         first(po, pn, xprev, xcur, pend);
         head_plain_launch<KSV()>(pn, lab, w, B, stream);
@@ -738,9 +777,11 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
 void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, float lr,
                                   const float* x, const int* labels, int nbatches, int pos, int n,
                                   float* ws, int* ctr, float* stats, int stats_ring, int B,
-                                  hipStream_t stream, int flush, const MlpOpt& o) {
+                                  hipStream_t stream, int flush, const MlpOpt& o,
+                                  const MlpDrop* drop) {
   check_b(B);
   check_opt(o, "mlp_run_pipelined_opt");
+  if (drop) check_drop(*drop, "mlp_run_pipelined_opt");
   if (!p0 || !p1 || p0 == p1 || !x || !labels || !ctr || !ws || nbatches < 1 || pos < 0 ||
       pos >= nbatches || n < 0 || (cur != 0 && cur != 1))
     throw std::runtime_error("mlp_run_pipelined_opt: bad buffers / position / count");
@@ -752,7 +793,7 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
                   const int* lab, int pend, int par) {
     lean_first_opt_launch<true>(po, pn, lr, xprev, xcur, ws, ctr, stats, stats_ring, B, pend, par,
                                 o, stream);
-    lean_head_launch(pn, lab, ws, B, stream);
+    lean_head_launch(pn, lab, ws, B, stream, drop);
   };
   auto apply = [&](const float* po, float* pn, const float* xprev, int par) {
     lean_first_opt_launch<false>(po, pn, lr, xprev, xprev, ws, ctr, stats, stats_ring, B, 1, par, o,

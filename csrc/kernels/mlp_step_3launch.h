@@ -36,9 +36,20 @@
 // mlp_wgrad after it has used the value as the stats-ring index; no other
 // thread of any launch touches it.
 #pragma once
+#include "mlp_step_api.h"
 #include "mlp_step_opt.h"
 #include "mlp_step_ws.h"
 #include "mlp_step_xg.h"
+#include "philox.h"
+
+// Where the dropout mask's Philox rounds run in head_row (measured: profiles/dropout/README.md).
+//   0: pinned behind the loads' fence, ahead of the first use of a slab value
+//   1: behind the fence, not pinned: the compiler spreads the rounds over the per-plane adds,
+//      between the loads' waits (the default)
+//   2: after the slab sum (through a data dependence on it)
+#ifndef DTFX_MLP_DROP_PLACE
+#define DTFX_MLP_DROP_PLACE 1
+#endif
 
 namespace dtfx {
 namespace mlp {
@@ -139,20 +150,30 @@ __global__ __launch_bounds__(64) void mlp_fwd_kernel(
 // scalar load.  Loads from a `const __restrict__` kernel argument are constant memory to the
 // compiler and carry no ordering against the fence, so the b1 / W2 / b2 loads go through a
 // laundered global pointer: ordinary loads, which stay in front of it.
+// DROP (MlpDrop, mlp_step_api.h): inverted dropout on h.  The step word is one more wave-uniform
+// scalar load at the head of the kernel, beside the label's; the lane's ONE Philox call (units
+// 2l, 2l + 1 share the counter (100 row + 2l) >> 2 and take words 0, 1 or 2, 3 of it) runs behind
+// the loads' fence, its ~60 integer VALU issues spread over the slab planes' adds between the
+// loads' waits (DTFX_MLP_DROP_PLACE above: pinned ahead of the first slab use it measured no
+// faster).  hbuf and the logits take the dropped, rescaled h; dz1 the mask factor
+// and the undropped h.  DROP = false compiles to the code without it.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false, int NGT = 0,
-          bool SB = false>
+          bool SB = false, bool DROP = false>
 __device__ __forceinline__ void head_row(
     const int row, const int lane, const float* __restrict__ p_old,
     const float* __restrict__ grad, float lr, float* __restrict__ p_new,
     const int* __restrict__ labels, const Bufs& w, int B, unsigned long long* __restrict__ tr,
-    const MlpXg& xg, float* __restrict__ dz1A) {
+    const MlpXg& xg, float* __restrict__ dz1A, const MlpDrop& da = MlpDrop{}) {
   static_assert(XW == 0 || (!APPLY && !TRACE), "the factor exchange runs the direct step");
+  static_assert(!DROP || (XW == 0 && !TRACE), "dropout: the lean head and the three-launch head");
   static_assert(!RM || (XW == 0 && !APPLY), "row-major factors: the single-GPU two-launch step");
   static_assert(!SB || (RM && NSLAB == KS3), "slab loads through a descriptor: the lean head");
   if (TRACE) trace_stamp(tr, row * 4 + 0);
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
   const int y = labels[row];
+  [[maybe_unused]] unsigned dstep = 0;  // DROP: global_step of this step (wave-uniform)
+  if constexpr (DROP) dstep = (unsigned)*da.ctr;
   // (an IEEE division sequence of 13 instructions; the asm pins it HERE, which in the ISA is
   // ahead of every operand load, not under the memory wait.  Computed behind the loads' fence
   // instead it measured the same: profiles/lean_prologue/)
@@ -248,26 +269,53 @@ __device__ __forceinline__ void head_row(
     }
   }
   if (TRACE) trace_stamp(tr, row * 4 + 1);
+  // DROP: mf[u] = scale where unit 2l + u is kept, else 0 (integer decisions only)
+  [[maybe_unused]] float mf[2] = {1.f, 1.f};
+  [[maybe_unused]] auto drop_mask = [&](unsigned dep) {  // (dep: 0, place 2's tie to the sum)
+    // (H % 4 == 0, j0 even: n & 3 is 0 or 2)
+    const unsigned n = (unsigned)row * H + (unsigned)j0 + dep;
+    const U4 r = philox10(U4{n >> 2, 0u, dstep, da.stream}, da.k0, da.k1);
+    const bool hi = (n & 2u) != 0;
+    mf[0] = ((hi ? r.z : r.x) >> 8) < da.thr ? da.scale : 0.f;
+    mf[1] = ((hi ? r.w : r.y) >> 8) < da.thr ? da.scale : 0.f;
+  };
+  if constexpr (DROP && DTFX_MLP_DROP_PLACE == 0) {
+    drop_mask(0u);
+    // (pinned here, under the loads' wait: nothing below may be scheduled ahead of the rounds)
+    asm volatile("" : "+v"(mf[0]), "+v"(mf[1]));
+  }
   f32x2 zp = {0.f, 0.f};  // (from 0, planes in order: 0 + (-0) is +0, a sum begun at plane 0 not)
 #pragma unroll
   for (int s = 0; s < NSLAB; ++s) zp += sv[s];
   const float zs[2] = {zp.x, zp.y};
+  if constexpr (DROP && DTFX_MLP_DROP_PLACE == 1) {
+    asm volatile("" ::"v"(zp.x), "v"(zp.y));
+    drop_mask(0u);  // (no dependence on the sum: scheduled between the waits above)
+  }
+  if constexpr (DROP && DTFX_MLP_DROP_PLACE == 2) {
+    unsigned dep = 0;
+    asm volatile("" : "+v"(dep) : "v"(zp.x), "v"(zp.y));
+    drop_mask(dep);
+  }
+  float hd[2];  // what the logits and hbuf take: h, or with DROP the dropped, rescaled h
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const float sg = sigmoidf_(zs[u] + b1v[u]);
     hv[u] = pv ? sg : 0.f;
+    if constexpr (DROP) hd[u] = hv[u] * mf[u];
+    else hd[u] = hv[u];
 #pragma unroll
     for (int c = 0; c < C; ++c) w2[u][c] = pv ? w2[u][c] : 0.f;
   }
   if (pv)
-    *reinterpret_cast<float2*>(&w.hbuf[(size_t)row * HP + 2 * lane]) = make_float2(hv[0], hv[1]);
+    *reinterpret_cast<float2*>(&w.hbuf[(size_t)row * HP + 2 * lane]) = make_float2(hd[0], hd[1]);
   // logits = h . W2 + b2: a reduce-scatter leaves class cl's logit on lane l, and the softmax
   // runs ONE class per lane -- one v_exp_f32 per lane, 16-lane row reductions for the max and
   // the denominator -- where all 64 lanes used to repeat the 10-class chains on the same ten
   // numbers (~400 VALU issues of the one wave, the head's compute span)
   float lgp[C];
 #pragma unroll
-  for (int c = 0; c < C; ++c) lgp[c] = hv[0] * w2[0][c] + hv[1] * w2[1][c];
+  for (int c = 0; c < C; ++c) lgp[c] = hd[0] * w2[0][c] + hd[1] * w2[1][c];
   const float lgc = wave_reduce_scatter(lgp, lane) + b2l;
   const float m = row_max16(clive ? lgc : -INFINITY);
   // first max, like tf.argmax: the lowest class whose logit equals the max
@@ -294,6 +342,7 @@ __device__ __forceinline__ void head_row(
       float dh = 0.f;
 #pragma unroll
       for (int c = 0; c < C; ++c) dh += dl[c] * w2[u][c];
+      if constexpr (DROP) dh *= mf[u];
       dzv[u] = dh * hv[u] * (1.f - hv[u]);
       if (!RM) w.dz1T[(size_t)j * BP + row] = dzv[u];
     }
@@ -327,6 +376,21 @@ __global__ __launch_bounds__(64) void mlp_head_kernel(
     unsigned long long* __restrict__ tr, MlpXg xg, float* __restrict__ dz1A) {
   head_row<APPLY, TRACE, XW, NSLAB, RM>(blockIdx.x, threadIdx.x, p_old, grad, lr, p_new, labels, w,
                                      B, tr, xg, dz1A);
+}
+
+// The three-launch head with dropout (the direct step, and the all-reduce engine's step_grad with
+// and without its deferred apply).  ctr apart: `const int* __restrict__`, so the step word is a
+// scalar load issued with the label's.
+template <bool APPLY>
+__global__ __launch_bounds__(64) void mlp_head_drop_kernel(
+    const float* __restrict__ p_old, const float* __restrict__ grad, float lr,
+    float* __restrict__ p_new, const int* __restrict__ labels, Bufs w, int B,
+    const int* __restrict__ ctr, unsigned k0, unsigned k1, unsigned thr, unsigned stream,
+    float scale) {
+  const MlpDrop da = {ctr, k0, k1, thr, stream, scale};
+  head_row<APPLY, false, 0, KS, false, 0, false, true>(blockIdx.x, threadIdx.x, p_old, grad, lr,
+                                                       p_new, labels, w, B, nullptr, MlpXg{},
+                                                       nullptr, da);
 }
 
 // ---------------------------------------------------------------------------

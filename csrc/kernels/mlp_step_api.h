@@ -10,6 +10,18 @@
 
 namespace dtfx {
 
+// ---- hidden-layer dropout of the step's head (ops/dropout.py has the definition).  Element
+// (batch row r, hidden unit j) is kept iff (w >> 8) < thr, w = word (n & 3), n = 100 r + j, of
+// philox4x32_10(counter {n >> 2, 0, *ctr, stream}, key {k0, k1}); kept values are scaled by
+// `scale` = 2^24 / thr.  ctr: the device global_step counter (equal to the step's own index at
+// every head launch: the only writer is the stats lane of the launch that records the step
+// before).  A null `const MlpDrop*` is no dropout and launches the plain kernels.
+struct MlpDrop {
+  const int* ctr;
+  unsigned k0, k1, thr, stream;
+  float scale;
+};
+
 // ---- workspace / layout queries and knobs
 long long mlp_workspace_floats(int B);
 void mlp_rowmajor_layout(int B, long long* out);
@@ -26,7 +38,7 @@ void mlp_fwd_launch(const float* p_old, const float* grad, float lr, float* p_ne
                     float* ws, int B, hipStream_t stream, unsigned long long* tr);
 void mlp_head_launch(const float* p_old, const float* grad, float lr, float* p_new,
                      const int* labels, float* ws, int B, hipStream_t stream,
-                     unsigned long long* tr);
+                     unsigned long long* tr, const MlpDrop* drop = nullptr);
 void mlp_wgrad_launch(float* p, float lr, float* grad, const float* x, float* ws, int* ctr,
                       float* stats, int stats_ring, int B, hipStream_t stream,
                       unsigned long long* tr);
@@ -44,7 +56,8 @@ void mlp_apply_launch(const float* p_old, float* p_new, float lr, const float* x
 void mlp_lean_fwdapply_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                               const float* x, float* ws, int* ctr, float* stats, int stats_ring,
                               int B, int stats_on, hipStream_t stream);
-void mlp_lean_head_launch(const float* p, const int* labels, float* ws, int B, hipStream_t stream);
+void mlp_lean_head_launch(const float* p, const int* labels, float* ws, int B, hipStream_t stream,
+                          const MlpDrop* drop = nullptr);
 void mlp_pipelined_trace_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                                 const float* x, const int* labels, float* ws, int* ctr,
                                 float* stats, int stats_ring, int B, hipStream_t stream,
@@ -52,7 +65,8 @@ void mlp_pipelined_trace_launch(const float* p_old, float* p_new, float lr, cons
                                 unsigned long long* trs);
 void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float lr, const float* x,
                               const int* labels, int nbatches, int pos, int n, float* ws, int* ctr,
-                              float* stats, int stats_ring, int B, hipStream_t stream, int flush);
+                              float* stats, int stats_ring, int B, hipStream_t stream, int flush,
+                              const MlpDrop* drop = nullptr);
 
 // ---- momentum / Adam / learning-rate schedules inside the lean two-launch step.  kind: 1
 // momentum, 2 adam; s0 / s1: the slot planes; tp: the int32[2] step pair; h0..h2:
@@ -76,7 +90,8 @@ void mlp_apply_opt_launch(const float* p_old, float* p_new, float lr, const floa
 void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, float lr,
                                   const float* x, const int* labels, int nbatches, int pos, int n,
                                   float* ws, int* ctr, float* stats, int stats_ring, int B,
-                                  hipStream_t stream, int flush, const MlpOpt& o);
+                                  hipStream_t stream, int flush, const MlpOpt& o,
+                                  const MlpDrop* drop = nullptr);
 void mlp_lr_sched_launch(const int* ctr, const int* blk, float lr0, float* out, float* lrs,
                          int ring, hipStream_t stream);
 

@@ -601,6 +601,19 @@ __global__ __launch_bounds__(64) void mlp_lean_head_kernel(const float* __restri
   lean_head_body<NGT, false>(p, labels, ws, B, nullptr);
 }
 
+// The lean head with dropout (MlpDrop by its words: 14 argument dwords, all preloaded).
+template <int NGT>
+__global__ __launch_bounds__(64) void mlp_lean_head_drop_kernel(
+    const float* __restrict__ p, const int* __restrict__ labels, float* __restrict__ ws, int B,
+    const int* __restrict__ ctr, unsigned k0, unsigned k1, unsigned thr, unsigned stream,
+    float scale) {
+  const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
+  const MlpDrop da = {ctr, k0, k1, thr, stream, scale};
+  head_row<false, false, 0, KS3, true, NGT, true, true>(blockIdx.x, threadIdx.x, p, p, 0.f,
+                                                        nullptr, labels, w, B, nullptr, MlpXg{},
+                                                        nullptr, da);
+}
+
 template <int NGT>
 __global__ __launch_bounds__(64) void mlp_lean_head_trace_kernel(
     const float* __restrict__ p, const int* __restrict__ labels, float* __restrict__ ws, int B,

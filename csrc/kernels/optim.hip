@@ -12,6 +12,7 @@
 // learning-rate schedule / step count instead of a frozen kernel argument.
 #include "common.h"
 #include "f32_api.h"
+#include "philox.h"
 
 #include <stdexcept>
 
@@ -163,22 +164,6 @@ void counter_add_launch(int* c, int d, hipStream_t s) {
 // mode 0: normal(a = mean, b = std)   1: uniform[a, b)
 // mode 2: truncated normal (|z| <= 2, redrawn), mean a, std b
 // ---------------------------------------------------------------------------
-struct U4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ U4 philox10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
-    const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0;
-    const unsigned hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
 __device__ __forceinline__ float u01(unsigned x) {  // (0, 1]
   return ((float)(x >> 8) + 1.f) * (1.f / 16777216.f);
 }

@@ -229,6 +229,15 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_integer("lr_warmup_steps", 0,
                    "linear warm-up: the rate of step s is scaled by min(1, (s + 1) / "
                    "lr_warmup_steps); 0 = none (also with --lr_schedule constant)", fv)
+    DEFINE_float("dropout", 0.0,
+                 "inverted dropout rate in [0, 1) on the MLP's hidden activation (a framework "
+                 "extension, tf.layers.dropout in training mode; evaluation never drops).  "
+                 "--strategy mirrored, --model mlp only: inside the fused step's head launch (one "
+                 "GPU), in the all-reduce engine (several) or on the autograd path (--device "
+                 "cpu); the mask is a pure function of (--dropout_seed, global_step, replica, "
+                 "row, unit), so a restored run resumes its sequence.  ps_async and --model "
+                 "bert|resnet50 refuse it; --job_name eval ignores it", fv)
+    DEFINE_integer("dropout_seed", 0, "--dropout: the mask generator's seed", fv)
     DEFINE_string("cpu_affinity", "numa",
                   "async PS: numa = the ps tasks on GPU 0's NUMA node (--numa_node overrides), "
                   "8 cores each; worker i on 2 cores of its OWN GPU's node, after the ps tasks' "

@@ -89,7 +89,14 @@ class MnistMLP(torch.nn.Module):
         logits = nn.dense(h, W2t, b2, None)
         return torch.softmax(logits, dim=-1), logits
 
-    def loss(self, x, labels):
-        """(mean xent, accuracy) of worker.py:59-68 / 87-90."""
-        _, logits = self.forward(x)
-        return nn.softmax_cross_entropy(logits, labels)
+    def loss(self, x, labels, keep=None, scale=1.0):
+        """(mean xent, accuracy) of worker.py:59-68 / 87-90.  ``keep`` (bool [B, 100], with
+        ``scale``: ``ops/dropout.py``): inverted dropout on the hidden activation, the fused
+        head's arithmetic -- kept units times ``scale``, dropped ones 0 -- in training mode."""
+        if keep is None:
+            _, logits = self.forward(x)
+            return nn.softmax_cross_entropy(logits, labels)
+        W1t, b1, W2t, b2 = self.views()
+        h = nn.dense(x, W1t, b1, "sigmoid")
+        hd = h * (keep.to(h.device, h.dtype) * scale)
+        return nn.softmax_cross_entropy(nn.dense(hd, W2t, b2, None), labels)

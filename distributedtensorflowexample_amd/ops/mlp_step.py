@@ -128,18 +128,38 @@ def _check_flat(*ts):
             raise ValueError("parameter/gradient buffers must be contiguous f32 [79510] on the GPU")
 
 
-def step_direct(p, x, labels, ws: StepWorkspace, lr, stats=True):
-    """One full SGD step in place on ``p`` for the batch (x [B,784], labels [B])."""
+def _head(h, p_old, grad, lr, p_new, labels, ws, s, dropout):
+    """The three-launch head, or with ``dropout`` (an ``ops.dropout.Dropout``) its DROP form."""
+    if dropout is None:
+        h.mlp_head(p_old, grad, lr, p_new, ptr(labels), ptr(ws.buf), ws.B, s)
+    else:
+        h.mlp_head_drop(p_old, grad, lr, p_new, ptr(labels), ptr(ws.buf), ws.B, s, ptr(ws.ctr),
+                        *dropout.args())
+
+
+def _lean_head(h, p, labels, ws, s, dropout):
+    """The lean head (row-major factors), or with ``dropout`` its DROP form."""
+    if dropout is None:
+        h.mlp_lean_head(ptr(p), ptr(labels), ptr(ws.buf), ws.B, s)
+    else:
+        h.mlp_lean_head_drop(ptr(p), ptr(labels), ptr(ws.buf), ws.B, s, ptr(ws.ctr),
+                             *dropout.args())
+
+
+def step_direct(p, x, labels, ws: StepWorkspace, lr, stats=True, dropout=None):
+    """One full SGD step in place on ``p`` for the batch (x [B,784], labels [B]).
+    ``dropout``: an ``ops.dropout.Dropout`` (the mask of step ``ws.ctr``), or None."""
     _check(x, labels, ws.B)
     _check_flat(p)
     h, s = hip(), stream_handle()
     h.mlp_fwd(ptr(p), 0, 0.0, 0, ptr(x), ptr(ws.buf), ws.B, s)
-    h.mlp_head(ptr(p), 0, 0.0, 0, ptr(labels), ptr(ws.buf), ws.B, s)
+    _head(h, ptr(p), 0, 0.0, 0, labels, ws, s, dropout)
     h.mlp_wgrad(ptr(p), float(lr), 0, ptr(x), ptr(ws.buf), ptr(ws.ctr),
                 ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, s)
 
 
-def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, stats=True):
+def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, stats=True,
+                   dropout=None):
     """Two-launch single-GPU step: ``mlp_lean_fwdapply`` applies the PREVIOUS step's SGD update
     (from the factors dz1/h/dlogits the last head left in ``ws`` and the previous batch
     ``x_prev``; W1 never materialises a gradient) reading ``p_old`` and writing ``p_new``,
@@ -149,7 +169,10 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     pair is the same arithmetic as ``mlp_fwdapply(ks=28)`` + ``mlp_head2(single=1)`` behind
     packed, preloaded kernel arguments, with phase A's operands requested first.
     ``apply=False`` (nothing pending): a plain copy + forward.  The
-    last step's update stays pending until ``flush_pipelined``."""
+    last step's update stays pending until ``flush_pipelined``.
+    ``dropout`` (an ``ops.dropout.Dropout``): the head drops hidden units by the mask of this
+    step's global_step, which it reads from ``ws.ctr`` -- the first launch has just recorded the
+    step before, so the counter is this step's index."""
     _check(x, labels, ws.B)
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
@@ -159,7 +182,7 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     h.mlp_lean_fwdapply(ptr(p_old), ptr(p_new), float(lr) if apply else 0.0,
                         ptr(x_prev if apply else x), ptr(x), ptr(ws.buf), ptr(ws.ctr),
                         ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, 1 if apply else 0, s)
-    h.mlp_lean_head(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s)  # (row-major factors)
+    _lean_head(h, p_new, labels, ws, s, dropout)  # (row-major factors)
 
 
 def flush_pipelined(p_old, p_new, x_prev, ws: StepWorkspace, lr, stats=True):
@@ -229,12 +252,12 @@ class PipelinedOpt:
 
 
 def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, par,
-                       opt: PipelinedOpt, stats=True):
+                       opt: PipelinedOpt, stats=True, dropout=None):
     """``step_pipelined`` with momentum / Adam: the first launch applies the pending update to
     ``p_old -> p_new`` AND, in place, to ``opt.slots`` (Adam's ``t`` = ``opt.tp[par] + 1``).
     ``apply=False`` is an explicit bit here: a copy + forward that leaves every slot byte alone.
     ``par``: the index of ``p_old`` in the caller's ping-pong pair; consecutive launches
-    alternate it.  The head launch is ``step_pipelined``'s."""
+    alternate it.  The head launch is ``step_pipelined``'s (``dropout`` too)."""
     _check(x, labels, ws.B)
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
@@ -251,7 +274,7 @@ def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, a
         h.mlp_lean_fwdapply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
                                 ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
                                 ws.stats_ring, ws.B, 1 if apply else 0, int(par), *opt.args(), s)
-    h.mlp_lean_head(ptr(p_new), ptr(labels), ptr(ws.buf), ws.B, s)
+    _lean_head(h, p_new, labels, ws, s, dropout)
 
 
 def flush_pipelined_opt(p_old, p_new, x_prev, ws: StepWorkspace, lr, par, opt: PipelinedOpt,
@@ -376,12 +399,12 @@ def flush_factor(p, x_prev, ws: StepWorkspace, lr, comm, dz1A, xstride, stats=Tr
 
 
 def step_grad(p_old, x, labels, ws: StepWorkspace, grad, prev_grad=None, lr=0.0, p_new=None,
-              stats=True):
+              stats=True, dropout=None):
     """Forward/backward writing ``grad``; optionally first applies ``prev_grad``.
 
     With ``prev_grad`` the step computes on ``p_new = p_old - lr * prev_grad``
     (published into ``p_new`` by the kernels) -- the deferred apply of sync DP.
-    Returns the parameter buffer the gradient belongs to.
+    Returns the parameter buffer the gradient belongs to.  ``dropout``: as ``step_direct``.
     """
     _check(x, labels, ws.B)
     _check_flat(p_old, grad, prev_grad, p_new)
@@ -391,7 +414,7 @@ def step_grad(p_old, x, labels, ws: StepWorkspace, grad, prev_grad=None, lr=0.0,
     pg = ptr(prev_grad)
     pn = ptr(p_new) if prev_grad is not None else 0
     h.mlp_fwd(ptr(p_old), pg, float(lr), pn, ptr(x), ptr(ws.buf), ws.B, s)
-    h.mlp_head(ptr(p_old), pg, float(lr), pn, ptr(labels), ptr(ws.buf), ws.B, s)
+    _head(h, ptr(p_old), pg, float(lr), pn, labels, ws, s, dropout)
     h.mlp_wgrad(0, 0.0, ptr(grad), ptr(x), ptr(ws.buf), ptr(ws.ctr),
                 ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, s)
     return p_new if prev_grad is not None else p_old

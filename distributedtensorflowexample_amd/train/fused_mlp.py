@@ -74,6 +74,16 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   ``ops.optim`` reads (``lr_tensor``), sgd included (in place, not the deferred apply).  The
   exchange engines, the persistent launch, the three-launch direct step, ``DTFX_MLP_KS=14``
   and the fused flush refuse a schedule.
+* ``dropout`` (``--dropout``; ``ops/dropout.py`` has the definition): inverted dropout on the
+  hidden activation, inside the head launch alone -- the logits and ``hbuf`` take the dropped,
+  rescaled h, dz1 the mask factor -- so every first launch (sgd, momentum, adam, scheduled,
+  shuffled) is the one it was.  The mask is Philox4x32-10 of (``dropout_seed``, global_step,
+  ``rank``, row, unit); the head reads the step from the device counter, so nothing is baked
+  into a graph or a host loop, a checkpoint carries nothing new and ``seek`` resumes the mask
+  sequence.  Recorded stats are training-mode values; ``evaluate`` / ``snapshot`` never drop.
+  Works in the two-launch step, the three-launch direct step and the all-reduce engine; the
+  exchange engines, the persistent launch, ``DTFX_MLP_KS=14`` and the fused flush refuse it.
+  ``dropout=0`` launches exactly today's kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -87,6 +97,7 @@ import time
 
 import torch
 
+from ..ops import dropout as dropout_mod
 from ..ops import lr_schedule as lr_schedule_mod
 from ..ops import mlp_step, optim
 from ..ops._ext import stream_handle
@@ -98,7 +109,18 @@ class FusedMLPTrainer:
                  world_size=1, stats_ring=4096, global_step=0, max_graph_steps=1024,
                  fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
-                 beta2=0.999, epsilon=1e-8, lr_schedule=None):
+                 beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0):
+        # --dropout: refused first where no head with the mask exists
+        self.drop = dropout_mod.resolve(dropout, dropout_seed, int(rank))
+        if self.drop is not None:
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("dropout: the exchange engines (fused_comm / factor_comm) have "
+                                 "no dropout variant; use the all-reduce engine")
+            if params.is_cuda and pipeline and allreduce is None and int(world_size) == 1:
+                from ..ops._ext import hip
+
+                if hip().mlp_single_ks() != 28:
+                    raise ValueError("dropout: DTFX_MLP_KS=14 has no dropout variant")
         # --lr_schedule: refused first where the rate is a by-value argument of every launch
         self.sched = lr_schedule_mod.resolve(lr_schedule)
         if self.sched is not None:
@@ -443,19 +465,20 @@ class FusedMLPTrainer:
                                self.fused_comm)
             return
         if self.direct:
-            mlp_step.step_direct(self.bufs[self.cur], xb, yb, self.ws, self.lr)
+            mlp_step.step_direct(self.bufs[self.cur], xb, yb, self.ws, self.lr, dropout=self.drop)
             return
         if self.pipelined and self.opt is not None:
             xp = self._xprev(p0)
             mlp_step.step_pipelined_opt(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
-                                        self.ws, self.lr, self.pending, self.cur, self.opt)
+                                        self.ws, self.lr, self.pending, self.cur, self.opt,
+                                        dropout=self.drop)
             self.cur ^= 1
             self.pending = True
             return
         if self.pipelined:
             xp = self._xprev(p0)
             mlp_step.step_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
-                                    self.ws, self.lr, apply=self.pending)
+                                    self.ws, self.lr, apply=self.pending, dropout=self.drop)
             self.cur ^= 1
             self.pending = True
             return
@@ -465,13 +488,14 @@ class FusedMLPTrainer:
             # through ops.optim in place, then the step without its deferred apply
             if self.pending:
                 self._apply_reduced(cur, self.opt.slots)
-            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad)
+            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop)
         elif self.pending:
             mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, prev_grad=self.grad,
-                               lr=self.lr / self.world_size, p_new=self.bufs[self.cur ^ 1])
+                               lr=self.lr / self.world_size, p_new=self.bufs[self.cur ^ 1],
+                               dropout=self.drop)
             self.cur ^= 1
         else:
-            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad)
+            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop)
         if self.allreduce is not None:
             self.allreduce(self.grad)
         self.pending = True
@@ -543,6 +567,9 @@ class FusedMLPTrainer:
             return
         if self.world_size > 1:
             return self._run_launched_engine(steps, flush)
+        if self.drop is not None and flush and _flush_fused():
+            raise ValueError("dropout: the fused flush (DTFX_MLP_FLUSH_FUSED) has no dropout "
+                             "variant")
         a = self._host_args
         if a is None:
             from ..ops._ext import hip, ptr
@@ -554,13 +581,17 @@ class FusedMLPTrainer:
                                            ptr(self.labels), self.nbatches, ptr(ws.buf),
                                            ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, self.B,
                                            *oargs)
+                if self.drop is not None:
+                    plan.set_drop(*self.drop.args())
                 a = self._host_args = (plan.run, self.device.index, None)
-            elif os.environ.get("DTFX_MLP_PLAN", "1") != "0":
+            elif self.drop is not None or os.environ.get("DTFX_MLP_PLAN", "1") != "0":
                 # the buffers bound once in a C++ plan: the call before the first kernel
                 # converts 7 arguments instead of 17 (a short timed region starts on the host)
                 plan = hip().MlpRunPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
                                         ptr(self.labels), self.nbatches, ptr(ws.buf),
                                         ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, self.B)
+                if self.drop is not None:
+                    plan.set_drop(*self.drop.args())
                 a = self._host_args = (plan.run, self.device.index, None)
             else:  # (A/B: the 17-argument entry point)
                 a = self._host_args = (hip().mlp_run_pipelined, self.device.index,
@@ -632,7 +663,7 @@ class FusedMLPTrainer:
         """The plain single-GPU step with batch <= 128 can run as ONE persistent launch (not in
         shuffle mode: that launch wraps around one dataset buffer inside the kernel)."""
         return (self.host_loop_ok and self.world_size == 1 and self.B <= 128
-                and not self.shuffle and self.opt is None)
+                and not self.shuffle and self.opt is None and self.drop is None)
 
     def run_persistent(self, steps, timeout_s=2.0, trace=None):
         """``steps`` complete SGD steps (every update applied, nothing left pending) in ONE
@@ -647,6 +678,8 @@ class FusedMLPTrainer:
         if self.sched is not None:
             raise ValueError("run_persistent: the persistent launch trains at a constant rate "
                              "(lr_schedule is not supported)")
+        if self.drop is not None:
+            raise ValueError("run_persistent: the persistent launch has no dropout variant")
         if not self.persistent_ok:
             raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
                                "(shuffle off, optimizer sgd)")
@@ -776,6 +809,17 @@ class FusedMLPTrainer:
             start = end - ring
         idx = torch.arange(start, end) % ring
         return r[idx.to(self.device)].cpu()
+
+
+def _flush_fused():
+    """Whether run_launched(.., flush=True) folds the flush into the last head (the opt-in
+    DTFX_MLP_FLUSH_FUSED form): the setter returns the previous setting, so read and restore."""
+    from ..ops._ext import hip
+
+    h = hip()
+    on = h.mlp_set_flush_fused(0)
+    h.mlp_set_flush_fused(on)
+    return bool(on)
 
 
 def benchmark_steps(trainer, steps, warmup, barrier=None, use_graph=True):

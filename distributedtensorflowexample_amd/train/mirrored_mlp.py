@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from ..models import mlp as mlp_model
+from ..ops import dropout as dropout_mod
 from ..ops import lr_schedule, mlp_step, nn, optim
 from ..ops.shuffle import shuffle_index
 from ..parallel import gpu_ps_optim
@@ -72,6 +73,13 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     sched = lr_schedule.from_flags(flags)
     if sched is not None and getattr(flags, "zero1", False):
         lr_schedule.refuse(flags, "--zero1 (the sharded update)")
+    # --dropout: in the fused step's head / the all-reduce engine's (train/fused_mlp.py), the
+    # same mask on the autograd path; a pure function of (seed, global_step, rank, row, unit)
+    drop_rate = dropout_mod.check_rate(getattr(flags, "dropout", 0.0) or 0.0)
+    drop_seed = int(getattr(flags, "dropout_seed", 0) or 0)
+    if drop_rate and getattr(flags, "zero1", False):
+        raise ValueError("--dropout does not support --zero1 (the sharded update)")
+    drop = dropout_mod.resolve(drop_rate, drop_seed, rank)
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -127,10 +135,10 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         fused = factor = x_all = None
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
-                and opt_kind == "sgd" and sched is None):
+                and opt_kind == "sgd" and sched is None and drop is None):
             # exchange engine (fused into the backward kernel / factor all-gather) when
-            # verified and faster than the all-reduce engine (sgd at a constant rate only: with
-            # an optimizer or a schedule the all-reduce engine it is)
+            # verified and faster than the all-reduce engine (sgd at a constant rate without
+            # dropout only: with an optimizer, a schedule or --dropout the all-reduce engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -152,7 +160,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              x_all=x_all if factor is not None else None, rank=rank,
                              pipeline=pipe if comm is not None else True,
                              shuffle=shuffle, shuffle_seed=shuffle_seed, optimizer=opt_kind,
-                             lr_schedule=sched, **opt_kw)
+                             lr_schedule=sched, dropout=drop_rate, dropout_seed=drop_seed,
+                             **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -190,7 +199,11 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                 ddp.reset()
             else:
                 model.flat.grad = None
-            loss, acc = model.loss(xb, yb)
+            if drop is None:
+                loss, acc = model.loss(xb, yb)
+            else:  # the mask of step i = global_step, this replica's stream
+                loss, acc = model.loss(xb, yb, keep=drop.keep_mask(i, xb.shape[0]),
+                                       scale=drop.scale)
             loss.backward()
             if zopt is not None:  # reduce-scatter -> owner SGD on 1/world -> all-gather
                 zopt.step()

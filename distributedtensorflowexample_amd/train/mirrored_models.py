@@ -41,6 +41,9 @@ def train_model_mirrored(flags, log=print):
     from ..ops import lr_schedule
 
     lr_schedule.refuse(flags, "--model %s" % flags.model)  # (before any process group / device)
+    from ..ops import dropout
+
+    dropout.refuse(flags, "--model %s" % flags.model)
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))

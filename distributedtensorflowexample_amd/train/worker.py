@@ -141,6 +141,10 @@ class Worker:
         from ..ops import lr_schedule
 
         lr_schedule.refuse(flags, "--strategy ps_async (--ps_device cpu and gpu)")
+        # --dropout: the parameter-server worker step has no dropped head
+        from ..ops import dropout
+
+        dropout.refuse(flags, "--strategy ps_async")
         if device is None or device == "auto":
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
