@@ -267,6 +267,37 @@ PYBIND11_MODULE(_hip, m) {
         dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(blk), h0, h1, h2, 1, P<float>(lrs)},
         S(s));
   }, "the flush of mlp_lean_fwdapply_sched");
+  // The same two launches with weight decay / Nesterov momentum (ops/weight_decay.py): kind 0
+  // (sgd), 1, 2; sched != 0: tp is the schedule block and lrs the rate ring, else the plain step
+  // pair and lrs = 0; l2, dec, na, nb: WeightDecay.words().
+  static const auto wd_opt = [](int kind, uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0,
+                                float h1, float h2, int sched, uintptr_t lrs, float l2, float dec,
+                                float na, float nb) {
+    return dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(tp), h0, h1, h2, sched ? 1 : 0,
+                        P<float>(lrs), 1, l2, dec, na, nb};
+  };
+  m.def("mlp_lean_fwdapply_wd", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                                   uintptr_t x, uintptr_t ws, uintptr_t ctr, uintptr_t stats,
+                                   int ring, int B, int apply, int par, int kind, uintptr_t s0,
+                                   uintptr_t s1, uintptr_t tp, float h0, float h1, float h2,
+                                   int sched, uintptr_t lrs, float l2, float dec, float na,
+                                   float nb, uintptr_t s) {
+    dtfx::mlp_lean_fwdapply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<const float>(x),
+        P<float>(ws), P<int>(ctr), P<float>(stats), ring, B, apply, par,
+        wd_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb), S(s));
+  }, "mlp_lean_fwdapply_opt / _sched with weight decay (L2 or decoupled) and Nesterov momentum "
+     "in the owning lane's update; apply=0 is still a pure copy");
+  m.def("mlp_apply_wd", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                           uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int par,
+                           int kind, uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1,
+                           float h2, int sched, uintptr_t lrs, float l2, float dec, float na,
+                           float nb, uintptr_t s) {
+    dtfx::mlp_apply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<float>(ws),
+        P<int>(ctr), P<float>(stats), ring, B, par,
+        wd_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb), S(s));
+  }, "the flush of mlp_lean_fwdapply_wd");
   m.def("mlp_lr_sched", [](uintptr_t ctr, uintptr_t blk, float lr0, uintptr_t out, uintptr_t lrs,
                            int ring, uintptr_t s) {
     dtfx::mlp_lr_sched_launch(P<const int>(ctr), P<const int>(blk), lr0, P<float>(out),
@@ -291,6 +322,14 @@ PYBIND11_MODULE(_hip, m) {
         return MlpRunOptPlan{bound(p0, p1, x, lab, nbatches, ws, ctr, stats, ring, B),
                              dtfx::MlpOpt{kind, P<float>(s0), P<float>(s1), P<int>(blk), h0, h1,
                                           h2, 1, P<float>(lrs)}};
+      }))
+      .def(py::init([](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
+                       uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int kind,
+                       uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1, float h2,
+                       int sched, uintptr_t lrs, float l2, float dec, float na, float nb) {
+        // the weight-decay / Nesterov form (mlp_lean_fwdapply_wd)
+        return MlpRunOptPlan{bound(p0, p1, x, lab, nbatches, ws, ctr, stats, ring, B),
+                             wd_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb)};
       }))
       .def("run", [](const MlpRunOptPlan& p, int cur, int pending, float lr, int pos, int n,
                      int flush, uintptr_t s) {

@@ -61,7 +61,9 @@ __global__ __launch_bounds__(256) void gps_apply_kernel(float* __restrict__ p,
 
 // ---------------------------------------------------------------------------------------------
 // Stateful optimizers (--optimizer momentum | adam): ops/optim.py's formulas (optim.hip's
-// momentum_kernel / adam_kernel) with weight_decay = 0 and no Nesterov, on the store's planes.
+// momentum_kernel / adam_kernel) on the store's planes.  The store applies them with weight_decay
+// = 0 and without Nesterov: those terms exist in the fused MLP trainer's first launch
+// (mlp_step_opt.h, the WD family) and ps_async refuses --weight_decay / --nesterov.
 //   momentum  accum = mu * accum + g;  p -= lr * accum                        slot0 = accum
 //   adam      m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * g * g       slot0 = m, slot1 = v
 //             p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)

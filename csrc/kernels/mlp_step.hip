@@ -6,7 +6,8 @@
 //   mlp_model.h          sizes, flat parameter layout (shared with mlp_persistent / mlp_eval)
 //   mlp_step_ws.h        K slicing, workspace layout (Bufs / ws_layout), the MFMA operand layout
 //   mlp_step_xg.h        xGMI exchange engines: xg_exchange*, head_allgather
-//   mlp_step_opt.h       momentum / Adam / learning-rate schedules: OptArgs, sched_rate, opt_update
+//   mlp_step_opt.h       momentum / Adam / learning-rate schedules / weight decay and Nesterov:
+//                        OptArgs, sched_rate, opt_update
 //   mlp_step_3launch.h   the three-launch step: mlp_fwd, head_row / mlp_head, wgrad_small / mlp_wgrad
 //   mlp_step_fwdapply.h  the two-launch step: fwdapply_block, lean entry points, the fused flush
 //   mlp_step_factor.h    the factor engines: mlp_fwdapply_factor / mlp_wgrad_factor
@@ -23,6 +24,7 @@
 #include "mlp_step_factor.h"
 #include "mlp_step_fwdapply.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -572,9 +574,19 @@ void mlp_head2_single_launch(const float* p, const int* labels, float* ws, int B
 // sched != 0: the scheduled instantiations (mlp_lean_fwdapply_sched_kernel) -- tp then heads the
 // 8-word schedule block, lr is the base rate, lrs the rate ring (f32 [stats_ring], or null), and
 // kind 0 is scheduled gradient descent (no slot planes).  (struct MlpOpt: mlp_step_api.h)
+// wd != 0: the weight-decay / Nesterov instantiations (mlp_lean_fwdapply_wd_kernel) with the
+// coefficients l2, dec, na, nb (ops/weight_decay.py: words()); kind 0 is then allowed at a
+// constant rate too (tp: the plain step pair, no slot plane).
 static void check_opt(const MlpOpt& o, const char* who) {
   const char* bad = nullptr;  // (the message is put together only when there is one)
-  if (o.sched) {  // (scheduled gradient descent is kind 0 and has no slot plane)
+  if (o.wd && !o.sched) {
+    if (o.kind != mlp::OPT_SGD && o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
+      bad = ": weight-decay optimizer kind must be 0 (sgd), 1 or 2";
+    else if (mlp_single_ks() != mlp::KS3)
+      bad = ": DTFX_MLP_KS=14 has no weight-decay variant";
+    else if (!o.tp || (o.kind != mlp::OPT_SGD && !o.s0) || (o.kind == mlp::OPT_ADAM && !o.s1))
+      bad = ": null slot plane / step pair";
+  } else if (o.sched) {  // (scheduled gradient descent is kind 0 and has no slot plane)
     if (o.kind != mlp::OPT_SGD && o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
       bad = ": scheduled optimizer kind must be 0 (sgd), 1 or 2";
     else if (mlp_single_ks() != mlp::KS3)
@@ -593,6 +605,8 @@ static void check_opt(const MlpOpt& o, const char* who) {
   }
   if (!bad && ((reinterpret_cast<uintptr_t>(o.s0) | reinterpret_cast<uintptr_t>(o.s1)) & 15))
     bad = ": slot planes must be 16-byte aligned";
+  if (!bad && o.wd && !(o.l2 >= 0.f && o.dec >= 0.f && o.l2 < INFINITY && o.dec < INFINITY))
+    bad = ": weight decay must be finite and >= 0";
   if (bad) throw std::runtime_error(std::string(who) + bad);
 }
 
@@ -610,7 +624,16 @@ static void lean_first_opt_launch(const float* p_old, float* p_new, float lr, co
   // (check_opt has admitted the kind: 0..2 scheduled, 1..2 not)
   const char* bad_kind = "fused MLP step: optimizer kind out of range";
   with_ngt(B, [&](auto NGT) {
-    if (o.sched)
+    if (o.wd)
+      with_const<OPT_SGD, OPT_MOMENTUM, OPT_ADAM>(o.kind, bad_kind, [&](auto OPTK) {
+        with_flag(o.sched != 0, [&](auto SCHED) {
+          hipLaunchKernelGGL((mlp_lean_fwdapply_wd_kernel<NGT(), FWD, OPTK(), SCHED()>), grid,
+                             block, 0, stream, p_old, p_new, x_prev, x, ws, lr, flags, ctr, stats,
+                             o.s0, o.s1, o.tp, o.h0, o.h1, o.h2, oflags, SCHED() ? o.lrs : nullptr,
+                             o.l2, o.dec, o.na, o.nb);
+        });
+      });
+    else if (o.sched)
       with_const<OPT_SGD, OPT_MOMENTUM, OPT_ADAM>(o.kind, bad_kind, [&](auto OPTK) {
         hipLaunchKernelGGL((mlp_lean_fwdapply_sched_kernel<NGT(), FWD, OPTK()>), grid, block, 0,
                            stream, p_old, p_new, x_prev, x, ws, lr, flags, ctr, stats, o.s0, o.s1,
@@ -788,7 +811,9 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
   if (flush && mlp_flush_fused())
     throw std::runtime_error(
         std::string("mlp_run_pipelined_opt: the fused flush (DTFX_MLP_FLUSH_FUSED) has ") +
-        (o.sched ? "no learning-rate schedule variant" : "no optimizer variant (sgd only)"));
+        (o.wd      ? "no weight-decay variant"
+         : o.sched ? "no learning-rate schedule variant"
+                   : "no optimizer variant (sgd only)"));
   auto step = [&](const float* po, float* pn, const float* xprev, const float* xcur,
                   const int* lab, int pend, int par) {
     lean_first_opt_launch<true>(po, pn, lr, xprev, xcur, ws, ctr, stats, stats_ring, B, pend, par,

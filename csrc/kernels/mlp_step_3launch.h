@@ -410,7 +410,9 @@ __global__ __launch_bounds__(64) void mlp_head_drop_kernel(
 // OPT (the lean step's optimizer variants; DIRECT, no exchange): the owning lane also reads and
 // rewrites its slot values (addresses clamped like p_src's, stores behind the p store's
 // predicate and oa.apply); the stats lane hands the step word on (tp[par ^ 1]).
-template <bool DIRECT, int NGT, int XW, bool RM = false, int OPT = OPT_SGD, bool SCHED = false>
+// WD: the weight-decay / Nesterov family (opt_update<OPT, WD>); decay reaches b1 / W2 / b2 here.
+template <bool DIRECT, int NGT, int XW, bool RM = false, int OPT = OPT_SGD, bool SCHED = false,
+          bool WD = false>
 __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx,
                                             float* __restrict__ p, float lr,
                                             float* __restrict__ grad, const Bufs& w,
@@ -418,7 +420,7 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
                                             int stats_ring, int B, const MlpXg& xg,
                                             const float* __restrict__ p_src = nullptr,
                                             int stats_on = 1, const OptArgs& oa = OptArgs{}) {
-  constexpr bool OX = OPT != OPT_SGD || SCHED;  // the OptArgs path (scheduled sgd: no slots)
+  constexpr bool OX = OPT != OPT_SGD || SCHED || WD;  // the OptArgs path (sgd: no slots)
   static_assert(!OX || (DIRECT && XW == 0), "optimizer variants: the lean step only");
   if (p_src == nullptr) p_src = p;
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
@@ -529,7 +531,7 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   (void)db2;
   __builtin_amdgcn_sched_barrier(0);
   [[maybe_unused]] OptCoef oc = {};  // (adam's b1^t / b2^t while the loads are in flight)
-  if constexpr (OX) oc = opt_coef<OPT, SCHED>(lr, oa);
+  if constexpr (OX) oc = opt_coef<OPT, SCHED, WD>(lr, oa);
   // NB: padded batch columns of dz1T/dlT are zero, so multiplying by 1 is exact.
   f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
 #pragma unroll
@@ -587,7 +589,7 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // (computed by every lane and selected: oa.apply == 0 copies p and leaves the slots)
-      const float pn = opt_update<OPT>(pv[i], v[i], sa[i], sb[i], oc);
+      const float pn = opt_update<OPT, WD>(pv[i], v[i], sa[i], sb[i], oc);
       if (ok[i]) {
         p[off[i]] = oa.apply ? pn : pv[i];
         if constexpr (OPT != OPT_SGD) {

@@ -79,6 +79,12 @@ struct MlpOpt {
   int sched = 0;         // != 0: the scheduled instantiations (tp heads the 8-word schedule block;
                          // kind 0 is then scheduled gradient descent)
   float* lrs = nullptr;  // their rate ring
+  // wd != 0: the weight-decay / Nesterov instantiations (ops/weight_decay.py: words()).  g' =
+  // g + l2 * p feeds every kind; adam's parameter also loses rate * dec * p (AdamW); momentum
+  // applies rate * (na * g' + nb * accum) -- (0, 1) plain, (1, mu) Nesterov.  kind 0 is then
+  // gradient descent with the step pair and no slot plane, scheduled or not.
+  int wd = 0;
+  float l2 = 0.f, dec = 0.f, na = 0.f, nb = 1.f;
 };
 void mlp_lean_fwdapply_opt_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                                   const float* x, float* ws, int* ctr, float* stats,

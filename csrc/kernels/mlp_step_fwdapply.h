@@ -89,8 +89,11 @@ namespace mlp {
 // slots; the new slot values go back through the p_new store's predicate.  The update is
 // computed by every lane and selected by oa.apply (no branch around the loads' uses, which
 // would let the compiler sink them below the barrier).
+// WD (weight decay / Nesterov; see OptArgs): the same item with opt_update<OPT, WD> -- pw4 is the
+// decayed value, so no load is added; apply == 0 stays the copy.
 template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true,
-          bool ORD = false, bool A16 = false, int OPT = OPT_SGD, bool SCHED = false>
+          bool ORD = false, bool A16 = false, int OPT = OPT_SGD, bool SCHED = false,
+          bool WD = false>
 __device__ __forceinline__ void fwdapply_block(
     const int bid, const float* __restrict__ p_old, float* __restrict__ p_new, float lr,
     const float* __restrict__ x_prev, const float* __restrict__ x, const Bufs& w,
@@ -99,7 +102,7 @@ __device__ __forceinline__ void fwdapply_block(
     unsigned long long* __restrict__ trs = nullptr, const OptArgs& oa = OptArgs{}) {
   static_assert(!ORD || (XW == 0 && KSX == KS3), "load order of the row-quad form");
   static_assert(!A16 || ORD, "the 16-byte apply belongs to the lean step");
-  constexpr bool OX = OPT != OPT_SGD || SCHED;  // the OptArgs path (scheduled sgd: no slots)
+  constexpr bool OX = OPT != OPT_SGD || SCHED || WD;  // the OptArgs path (sgd: no slots)
   static_assert(!OX || (A16 && !TRACE), "optimizer variants: the lean step only");
   // stamps per wave: 0 entry, 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab
   // stored; with XW > 0 also 4 local gradient slice ready (exchange starts), 5 two-shot: the
@@ -123,8 +126,8 @@ __device__ __forceinline__ void fwdapply_block(
   if (bid >= HT * KSX) {
     const int jt = bid - HT * KSX;
     if constexpr (OX)
-      wgrad_small<true, NGT, XW, RM, OPT, SCHED>(jt, wave, lane, 0, p_new, lr, nullptr, w, ctr,
-                                                 stats, stats_ring, B, xg, p_old, stats_on, oa);
+      wgrad_small<true, NGT, XW, RM, OPT, SCHED, WD>(jt, wave, lane, 0, p_new, lr, nullptr, w, ctr,
+                                                     stats, stats_ring, B, xg, p_old, stats_on, oa);
     else
     wgrad_small<true, NGT, XW, RM>(jt, wave, lane, MLP_XG_SMALL_EPOCH + jt * 4 + wave, p_new, lr,
                                nullptr, w, ctr, stats, stats_ring, B, xg, p_old, stats_on);
@@ -218,7 +221,7 @@ __device__ __forceinline__ void fwdapply_block(
     __builtin_amdgcn_sched_barrier(0);  // all loads in flight together
     // (OPT: adam's b1^t / b2^t while the loads are in flight, not between the sum and the store)
     [[maybe_unused]] OptCoef oc = {};
-    if constexpr (OX) oc = opt_coef<OPT, SCHED>(lr, oa);
+    if constexpr (OX) oc = opt_coef<OPT, SCHED, WD>(lr, oa);
     if constexpr (TRACE && NGT > 0 && FWD) {
       if (trs) {  // loads issued after the first class: ORD pw + xa, else pw + the factors
         unsigned long long* t2 = trs + (size_t)(bid * 4 + wave) * 2;
@@ -253,10 +256,10 @@ __device__ __forceinline__ void fwdapply_block(
       const bool live = jw < H;
       float4 v;
       if constexpr (OX) {
-        v.x = opt_update<OPT>(pw4.x, part.x, sa4.x, sb4.x, oc);
-        v.y = opt_update<OPT>(pw4.y, part.y, sa4.y, sb4.y, oc);
-        v.z = opt_update<OPT>(pw4.z, part.z, sa4.z, sb4.z, oc);
-        v.w = opt_update<OPT>(pw4.w, part.w, sa4.w, sb4.w, oc);
+        v.x = opt_update<OPT, WD>(pw4.x, part.x, sa4.x, sb4.x, oc);
+        v.y = opt_update<OPT, WD>(pw4.y, part.y, sa4.y, sb4.y, oc);
+        v.z = opt_update<OPT, WD>(pw4.z, part.z, sa4.z, sb4.z, oc);
+        v.w = opt_update<OPT, WD>(pw4.w, part.w, sa4.w, sb4.w, oc);
         if (!oa.apply) v = pw4;  // nothing pending: a copy, and no slot byte is written
         if constexpr (OPT != OPT_SGD) {
           if (oa.apply && lane < IPW && live) {
@@ -518,7 +521,7 @@ __global__ __launch_bounds__(256) void mlp_fwdapply_kernel(
 // The data-parallel engines, mlp_fwdapply_launch / mlp_head2_launch and the opt-in fused flush
 // keep mlp_fwdapply_kernel / mlp_head_kernel.
 
-template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD, bool SCHED = false>
+template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD, bool SCHED = false, bool WD = false>
 __device__ __forceinline__ void lean_fwdapply_body(
     const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
     const float* __restrict__ x, float* __restrict__ ws, int* __restrict__ ctr,
@@ -526,7 +529,11 @@ __device__ __forceinline__ void lean_fwdapply_body(
     unsigned long long* __restrict__ trs, const OptArgs& oa = OptArgs{}) {
   const int B = flags & 511, stats_on = (flags >> 9) & 1, stats_ring = flags >> 10;
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
-  if constexpr (OPT != OPT_SGD || SCHED)
+  if constexpr (WD)
+    fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT, SCHED, true>(
+        blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{},
+        tr, trs, oa);
+  else if constexpr (OPT != OPT_SGD || SCHED)
     fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT, SCHED>(
         blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{},
         tr, trs, oa);
@@ -573,6 +580,22 @@ __global__ __launch_bounds__(256) void mlp_lean_fwdapply_sched_kernel(
   const OptArgs oa = {s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1, lrs};
   lean_fwdapply_body<NGT, false, FWD, OPT, true>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags,
                                                  nullptr, nullptr, oa);
+}
+
+// The weight-decay / Nesterov instantiations (OptArgs' WD coefficients): the scheduled kernel's
+// arguments and the four coefficient words l2, dec, na, nb.  SCHED = false: tp is the plain step
+// pair, lr the rate itself and lrs unused.  Every kind, sgd included, takes the explicit apply
+// bit; sgd has no slot plane.
+template <int NGT, bool FWD, int OPT, bool SCHED>
+__global__ __launch_bounds__(256) void mlp_lean_fwdapply_wd_kernel(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, float lr, int flags,
+    int* __restrict__ ctr, float* __restrict__ stats, float* __restrict__ s0,
+    float* __restrict__ s1, int* __restrict__ tp, float h0, float h1, float h2, int oflags,
+    float* __restrict__ lrs, float l2, float dec, float na, float nb) {
+  const OptArgs oa = {s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1, lrs, l2, dec, na, nb};
+  lean_fwdapply_body<NGT, false, FWD, OPT, SCHED, true>(p_old, p_new, x_prev, x, ws, ctr, stats,
+                                                        lr, flags, nullptr, nullptr, oa);
 }
 
 template <int NGT>

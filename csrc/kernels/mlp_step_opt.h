@@ -16,11 +16,11 @@ namespace mlp {
 
 // ---------------------------------------------------------------------------
 // Stateful optimizers inside the lean two-launch step (mlp_lean_fwdapply_opt_kernel): gpu_ps.hip's
-// formulas (ops/optim.py's momentum_ / adam_, no weight decay, no Nesterov) applied by the lane
-// that owns the element -- the A16 item of fwdapply_block for W1, the ok[i] lane of wgrad_small
-// for b1 / W2 / b2.  The slot planes s0 (momentum: accum; adam: m) and s1 (adam: v) are flat f32
-// [NPARAM] buffers in the parameter layout, updated IN PLACE (one owner per element, read once
-// and written once by it); only the parameters ping-pong.
+// formulas (ops/optim.py's momentum_ / adam_; weight decay and Nesterov: the WD family below)
+// applied by the lane that owns the element -- the A16 item of fwdapply_block for W1, the ok[i]
+// lane of wgrad_small for b1 / W2 / b2.  The slot planes s0 (momentum: accum; adam: m) and s1
+// (adam: v) are flat f32 [NPARAM] buffers in the parameter layout, updated IN PLACE (one owner
+// per element, read once and written once by it); only the parameters ping-pong.
 //   momentum  accum = mu * accum + g;  p -= lr * accum   (mu = 0: accum = g and the SGD bits)
 //   adam      m = b1 * m + (1 - b1) * g;  v = b2 * v + (1 - b2) * g * g
 //             p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
@@ -38,7 +38,19 @@ struct OptArgs {
   float h0, h1, h2;  // momentum: mu; adam: beta1, beta2, epsilon
   int apply, par;
   float* lrs;        // SCHED: the rate ring (f32 [stats_ring], parallel to the stats ring), or null
+  // WD (mlp_lean_fwdapply_wd_kernel): wave-uniform coefficients, read by that family alone
+  float l2 = 0.f, dec = 0.f, na = 0.f, nb = 1.f;
 };
+// Weight decay and Nesterov momentum (the WD instantiations; ops/weight_decay.py is the
+// definition, which is ops/optim.py's and torch.optim's).  g' = g + l2 * p is the gradient
+// every kind uses -- the parameter is already in the owning lane's registers -- and
+//   sgd       p -= rate * g'
+//   momentum  accum = mu * accum + g';  p -= rate * (na * g' + nb * accum)
+//             (na, nb) = (0, 1) plain, (1, mu) Nesterov: one instantiation for both
+//   adam      m, v take g';  p = (p - rate * dec * p) - (rate / (1 - b1^t)) * m / (...)
+//             adamw: l2 = 0, dec = wd (decoupled);  not adamw: l2 = wd, dec = 0
+// rate is the rate of the step applied: sched_rate's value with a schedule, never adam's
+// bias-corrected c.lr.  Decay is uniform over the flat buffer, biases included.
 // Learning-rate schedules evaluated on the device (the SCHED instantiations; ops/lr_schedule.py
 // is the definition, its value_f32 this arithmetic operation for operation).  The step pair is
 // then the head of an 8-word block [tp0, tp1, kind | staircase << 2, decay_steps, a, inv_decay,
@@ -72,16 +84,19 @@ __device__ __forceinline__ float sched_rate(float lr0, int s, const SchedBlock& 
   return inv_warm > 0.f ? lr * warm : lr;
 }
 // momentum: lr, h0 = mu.  adam: lr = lr / (1 - b1^t), rbc2 = 1 / sqrt(1 - b2^t)
+// WD: l2, rd = rate * dec, na, nb (lr stays the rate for sgd and momentum)
 struct OptCoef {
   float lr, h0, h1, h2, rbc2;
+  float l2, rd, na, nb;
 };
-template <int OPT, bool SCHED = false>
+template <int OPT, bool SCHED = false, bool WD = false>
 __device__ __forceinline__ OptCoef opt_coef(float lr, const OptArgs& oa) {
   if constexpr (SCHED) {  // the applied step's rate
     const SchedBlock w = sched_load(oa.tp);
     lr = sched_rate(lr, oa.par ? w.lo.y : w.lo.x, w);
   }
   OptCoef c = {lr, oa.h0, oa.h1, oa.h2, 1.f};
+  if constexpr (WD) c.l2 = oa.l2, c.rd = lr * oa.dec, c.na = oa.na, c.nb = oa.nb;
   if constexpr (OPT == OPT_ADAM) {  // (wave-uniform: once per wave, not per element)
     // b^t = exp2(t log2 b) on the transcendental unit: 0 <= b < 1, so the product is <= 0, and
     // wherever b^t is not negligible against 1 (t |log2 b| < 24) its relative error stays below
@@ -94,10 +109,23 @@ __device__ __forceinline__ OptCoef opt_coef(float lr, const OptArgs& oa) {
   return c;
 }
 // -> the new parameter value; s0 / s1 become the new slot values
-template <int OPT>
+template <int OPT, bool WD = false>
 __device__ __forceinline__ float opt_update(float p, float g, float& s0, float& s1,
                                             const OptCoef& c) {
-  if constexpr (OPT == OPT_SGD) {  // (scheduled gradient descent: the SGD step's own expression)
+  if constexpr (WD) {  // (optim.hip's expressions; one or two fmas per element on top)
+    const float gg = g + c.l2 * p;
+    if constexpr (OPT == OPT_SGD) {
+      return p - c.lr * gg;
+    } else if constexpr (OPT == OPT_MOMENTUM) {
+      s0 = c.h0 * s0 + gg;
+      return p - c.lr * (c.na * gg + c.nb * s0);
+    } else {
+      s0 = c.h0 * s0 + (1.f - c.h0) * gg;
+      s1 = c.h1 * s1 + (1.f - c.h1) * gg * gg;
+      const float pd = p - c.rd * p;
+      return pd - c.lr * s0 * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(s1) * c.rbc2 + c.h2);
+    }
+  } else if constexpr (OPT == OPT_SGD) {  // (scheduled gradient descent: the SGD step's own)
     return p - c.lr * g;
   } else if constexpr (OPT == OPT_MOMENTUM) {
     s0 = c.h0 * s0 + g;

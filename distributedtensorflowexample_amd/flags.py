@@ -238,6 +238,21 @@ def define_reference_flags(flag_values=FLAGS):
                  "row, unit), so a restored run resumes its sequence.  ps_async and --model "
                  "bert|resnet50 refuse it; --job_name eval ignores it", fv)
     DEFINE_integer("dropout_seed", 0, "--dropout: the mask generator's seed", fv)
+    DEFINE_float("weight_decay", 0.0,
+                 "weight decay >= 0 (torch.optim's definition, ops/weight_decay.py), uniform over "
+                 "all parameters, biases included: L2 (g + wd * p) for --optimizer sgd, momentum "
+                 "and adam with --noadamw; decoupled (p loses lr_t * wd * p, AdamW) for adam by "
+                 "default.  --strategy mirrored, --model mlp only: inside the fused step's first "
+                 "launch (one GPU), in the all-reduce engine (several) or on the autograd path "
+                 "(--device cpu).  ps_async, --model bert|resnet50 (they have their own) and "
+                 "--zero1 refuse it; --job_name eval ignores it", fv)
+    DEFINE_boolean("adamw", True,
+                   "--optimizer adam with --weight_decay: decoupled decay (AdamW); --noadamw: L2 "
+                   "through the moments (Adam).  Read only with --optimizer adam", fv)
+    DEFINE_boolean("nesterov", False,
+                   "--optimizer momentum: Nesterov momentum (tf.train.MomentumOptimizer's "
+                   "use_nesterov; p -= lr_t * (g' + mu * accum)); refused with any other "
+                   "--optimizer", fv)
     DEFINE_string("cpu_affinity", "numa",
                   "async PS: numa = the ps tasks on GPU 0's NUMA node (--numa_node overrides), "
                   "8 cores each; worker i on 2 cores of its OWN GPU's node, after the ps tasks' "

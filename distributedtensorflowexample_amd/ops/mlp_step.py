@@ -209,15 +209,24 @@ class PipelinedOpt:
     ``[tp0, tp1, kind | staircase << 2, decay_steps, a, inv_decay_steps, inv_warmup, 0]`` that a
     wave fetches at once (``tp`` stays an int32 [2] view of it), ``rates`` is the f32 rate ring
     parallel to the stats ring (index ``step % stats_ring``), and kind ``"sgd"`` is allowed:
-    scheduled gradient descent has the step pair and no slot plane."""
+    scheduled gradient descent has the step pair and no slot plane.
+
+    ``decay`` (an ``ops.weight_decay.WeightDecay``): the weight-decay / Nesterov instantiations
+    (``mlp_lean_fwdapply_wd``), scheduled or not; ``wd_args()`` appends the schedule flag, the
+    rate ring and the four coefficient words.  Kind ``"sgd"`` is allowed then too."""
 
     KINDS = {"momentum": 1, "adam": 2}
 
     def __init__(self, kind, device, momentum=0.9, beta1=0.9, beta2=0.999, epsilon=1e-8,
-                 schedule=None, stats_ring=4096):
+                 schedule=None, stats_ring=4096, decay=None):
         from ..parallel import gpu_ps_optim
 
-        if kind not in self.KINDS and not (kind == "sgd" and schedule is not None):
+        if decay is not None and decay.kind != kind:
+            raise ValueError("the weight-decay terms are %s's, the optimizer is %s"
+                             % (decay.kind, kind))
+        self.decay = decay
+        if kind not in self.KINDS and not (
+                kind == "sgd" and (schedule is not None or decay is not None)):
             raise ValueError("the fused step's optimizers are momentum and adam, got %r" % (kind,))
         self.kind = kind
         self.code = self.KINDS.get(kind, 0)
@@ -250,6 +259,13 @@ class PipelinedOpt:
         """``args()`` and the rate ring, as the scheduled launchers take them."""
         return self.args() + (ptr(self.rates) if stats else 0,)
 
+    def wd_args(self, stats=True):
+        """``args()``, the schedule flag, the rate ring (0 without a schedule) and the
+        coefficient words, as the weight-decay launchers take them."""
+        sched = self.schedule is not None
+        return (self.args() + (1 if sched else 0, ptr(self.rates) if (sched and stats) else 0)
+                + self.decay.words())
+
 
 def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, par,
                        opt: PipelinedOpt, stats=True, dropout=None):
@@ -264,7 +280,14 @@ def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, a
     if p_old.data_ptr() == p_new.data_ptr():
         raise ValueError("the pipelined step needs distinct ping-pong buffers")
     h, s = hip(), stream_handle()
-    if opt.schedule is not None:  # lr: the base rate; the kernel computes the applied step's
+    if opt.decay is not None:  # (lr: the base rate with a schedule, else the rate)
+        if opt.schedule is not None:
+            _check_sched(opt, ws)
+        h.mlp_lean_fwdapply_wd(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
+                               ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
+                               ws.stats_ring, ws.B, 1 if apply else 0, int(par),
+                               *opt.wd_args(stats), s)
+    elif opt.schedule is not None:  # lr: the base rate; the kernel computes the applied step's
         _check_sched(opt, ws)
         h.mlp_lean_fwdapply_sched(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
                                   ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
@@ -282,6 +305,13 @@ def flush_pipelined_opt(p_old, p_new, x_prev, ws: StepWorkspace, lr, par, opt: P
     """``flush_pipelined`` with momentum / Adam (the apply-only instantiation)."""
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
+    if opt.decay is not None:
+        if opt.schedule is not None:
+            _check_sched(opt, ws)
+        hip().mlp_apply_wd(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev), ptr(ws.buf),
+                           ptr(ws.ctr), ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B,
+                           int(par), *opt.wd_args(stats), stream_handle())
+        return
     if opt.schedule is not None:
         _check_sched(opt, ws)
         hip().mlp_apply_sched(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev), ptr(ws.buf),

@@ -84,6 +84,20 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   Works in the two-launch step, the three-launch direct step and the all-reduce engine; the
   exchange engines, the persistent launch, ``DTFX_MLP_KS=14`` and the fused flush refuse it.
   ``dropout=0`` launches exactly today's kernels.
+* ``weight_decay`` / ``adamw`` / ``nesterov`` (``--weight_decay``, ``--adamw``, ``--nesterov``;
+  ``ops/weight_decay.py`` has the definition, which is ``ops/optim.py``'s and ``torch.optim``'s):
+  L2 decay for sgd, momentum and ``adamw=False`` adam, decoupled decay for AdamW, and Nesterov
+  momentum, inside the lane expression that owns each element -- the W1 item of the first launch
+  and the small-parameter lanes (``mlp_lean_fwdapply_wd``: one instantiation per optimizer, at a
+  constant and at a scheduled rate).  The parameter is already in the lane's registers, so no
+  load and no launch is added; ``apply == 0`` stays a pure copy; the decoupled term uses the
+  rate of the step applied.  Decay is uniform over the flat buffer, biases included; the
+  recorded loss stays the cross-entropy.  Works with every optimizer, schedule, shuffle and
+  dropout through ``step()``, graph replay, ``run_launched``, ``flush``, ``snapshot``, ``seek``
+  and the all-reduce engine (``ops.optim``'s own arguments; sgd then applies in place).  The
+  exchange engines, the three-launch direct step, the persistent launch, ``DTFX_MLP_KS=14`` and
+  the fused flush refuse them.  ``weight_decay=0, nesterov=False`` launches exactly today's
+  kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -100,6 +114,7 @@ import torch
 from ..ops import dropout as dropout_mod
 from ..ops import lr_schedule as lr_schedule_mod
 from ..ops import mlp_step, optim
+from ..ops import weight_decay as weight_decay_mod
 from ..ops._ext import stream_handle
 from ..parallel import gpu_ps_optim
 
@@ -109,7 +124,26 @@ class FusedMLPTrainer:
                  world_size=1, stats_ring=4096, global_step=0, max_graph_steps=1024,
                  fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
-                 beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0):
+                 beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0,
+                 weight_decay=0.0, adamw=True, nesterov=False):
+        # --weight_decay / --nesterov: refused first where the update has no such term
+        self.decay = weight_decay_mod.resolve(gpu_ps_optim.check_kind(optimizer), weight_decay,
+                                              adamw, nesterov, momentum)
+        if self.decay is not None:
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("weight_decay / nesterov: the exchange engines (fused_comm / "
+                                 "factor_comm) apply plain gradient descent; use the all-reduce "
+                                 "engine")
+            if not pipeline and allreduce is None and int(world_size) == 1:
+                raise ValueError("weight_decay / nesterov: the three-launch direct step "
+                                 "(pipeline=False) has no weight-decay variant; use the "
+                                 "two-launch step (pipeline=True)")
+            if params.is_cuda and allreduce is None and int(world_size) == 1:
+                from ..ops._ext import hip
+
+                if hip().mlp_single_ks() != 28:
+                    raise ValueError("weight_decay / nesterov: DTFX_MLP_KS=14 has no "
+                                     "weight-decay variant; use the default K slicing")
         # --dropout: refused first where no head with the mask exists
         self.drop = dropout_mod.resolve(dropout, dropout_seed, int(rank))
         if self.drop is not None:
@@ -199,9 +233,10 @@ class FusedMLPTrainer:
         # lr_schedule: the same object also carries the schedule block and the rate ring, and
         # exists for scheduled sgd too (no slot plane) -- the scheduled step is an OptArgs one
         self.opt = None
-        if self.optimizer != "sgd" or self.sched is not None:
+        if self.optimizer != "sgd" or self.sched is not None or self.decay is not None:
             self.opt = mlp_step.PipelinedOpt(self.optimizer, self.device, momentum, beta1, beta2,
-                                             epsilon, schedule=self.sched, stats_ring=stats_ring)
+                                             epsilon, schedule=self.sched, stats_ring=stats_ring,
+                                             decay=self.decay)
             self.opt.set_step(global_step)
         # the all-reduce engine's scheduled rate (ops.optim's lr_tensor)
         self._lr_dev = (torch.zeros(1, device=self.device, dtype=torch.float32)
@@ -286,14 +321,16 @@ class FusedMLPTrainer:
         lrt = None
         if self.sched is not None:
             lrt = mlp_step.scheduled_rate(self.ws, self.opt, self.lr, self._lr_dev, publish)
+        d = self.decay  # (weight decay / Nesterov: the arguments ops.optim already takes)
         if self.optimizer == "sgd":
-            optim.sgd_(p, self.grad, self.lr, lr_tensor=lrt)
+            optim.sgd_(p, self.grad, self.lr, lr_tensor=lrt, **(d.sgd_kw if d else {}))
         elif self.optimizer == "momentum":
-            optim.momentum_(p, self.grad, slots[0], self.lr, momentum=h[0], lr_tensor=lrt)
+            optim.momentum_(p, self.grad, slots[0], self.lr, momentum=h[0], lr_tensor=lrt,
+                            **(d.momentum_kw if d else {}))
         else:
+            kw = d.adam_kw if d else dict(weight_decay=0.0, adamw=False)
             optim.adam_(p, self.grad, slots[0], slots[1], self.lr, 0, beta1=h[0], beta2=h[1],
-                        eps=h[2], weight_decay=0.0, adamw=False, step_tensor=self.ws.ctr,
-                        lr_tensor=lrt)
+                        eps=h[2], step_tensor=self.ws.ctr, lr_tensor=lrt, **kw)
 
     def flush(self):
         """Apply the pending update in place (DP: p -= lr/N * grad; pipelined: the last
@@ -570,13 +607,17 @@ class FusedMLPTrainer:
         if self.drop is not None and flush and _flush_fused():
             raise ValueError("dropout: the fused flush (DTFX_MLP_FLUSH_FUSED) has no dropout "
                              "variant")
+        if self.decay is not None and flush and _flush_fused():
+            raise ValueError("weight_decay / nesterov: the fused flush (DTFX_MLP_FLUSH_FUSED) has "
+                             "no weight-decay variant; flush in its own launch")
         a = self._host_args
         if a is None:
             from ..ops._ext import hip, ptr
 
             ws = self.ws
             if self.opt is not None:  # the optimizer form of the plan (slot pointers bound too)
-                oargs = self.opt.args() if self.sched is None else self.opt.sched_args()
+                oargs = (self.opt.wd_args() if self.decay is not None
+                         else self.opt.args() if self.sched is None else self.opt.sched_args())
                 plan = hip().MlpRunOptPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
                                            ptr(self.labels), self.nbatches, ptr(ws.buf),
                                            ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, self.B,
@@ -680,6 +721,9 @@ class FusedMLPTrainer:
                              "(lr_schedule is not supported)")
         if self.drop is not None:
             raise ValueError("run_persistent: the persistent launch has no dropout variant")
+        if self.decay is not None:
+            raise ValueError("run_persistent: the persistent launch has no weight-decay or "
+                             "Nesterov variant; use run() / run_launched()")
         if not self.persistent_ok:
             raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
                                "(shuffle off, optimizer sgd)")

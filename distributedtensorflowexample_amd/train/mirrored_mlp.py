@@ -22,6 +22,7 @@ import torch.distributed as dist
 from ..models import mlp as mlp_model
 from ..ops import dropout as dropout_mod
 from ..ops import lr_schedule, mlp_step, nn, optim
+from ..ops import weight_decay as weight_decay_mod
 from ..ops.shuffle import shuffle_index
 from ..parallel import gpu_ps_optim
 from ..parallel.comm import NativeComm, TorchComm
@@ -80,6 +81,12 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     if drop_rate and getattr(flags, "zero1", False):
         raise ValueError("--dropout does not support --zero1 (the sharded update)")
     drop = dropout_mod.resolve(drop_rate, drop_seed, rank)
+    # --weight_decay / --adamw / --nesterov: in the fused step's first launch / the all-reduce
+    # engine's ops.optim call (train/fused_mlp.py), the same ops.optim arguments on the autograd
+    # path; no new state, so checkpoints hold nothing new
+    decay = weight_decay_mod.from_flags(flags)
+    if decay is not None and getattr(flags, "zero1", False):
+        weight_decay_mod.refuse(flags, "--zero1 (the sharded update)")
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -135,10 +142,11 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         fused = factor = x_all = None
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
-                and opt_kind == "sgd" and sched is None and drop is None):
+                and opt_kind == "sgd" and sched is None and drop is None and decay is None):
             # exchange engine (fused into the backward kernel / factor all-gather) when
             # verified and faster than the all-reduce engine (sgd at a constant rate without
-            # dropout only: with an optimizer, a schedule or --dropout the all-reduce engine it is)
+            # dropout or weight decay only: with an optimizer, a schedule, --dropout or
+            # --weight_decay the all-reduce engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -161,7 +169,9 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              pipeline=pipe if comm is not None else True,
                              shuffle=shuffle, shuffle_seed=shuffle_seed, optimizer=opt_kind,
                              lr_schedule=sched, dropout=drop_rate, dropout_seed=drop_seed,
-                             **opt_kw)
+                             weight_decay=decay.wd if decay else 0.0,
+                             adamw=decay.adamw if decay else True,
+                             nesterov=decay.nesterov if decay else False, **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -220,14 +230,16 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             with torch.no_grad():
                 if opt_kind == "momentum":
                     optim.momentum_(model.flat.data, g, cpu_slots[0], lr,
-                                    momentum=opt_kw["momentum"])
+                                    momentum=opt_kw["momentum"],
+                                    **(decay.momentum_kw if decay else {}))
                 elif opt_kind == "adam":  # t = global_step + 1 of this step
                     optim.adam_(model.flat.data, g, cpu_slots[0], cpu_slots[1],
                                 lr, i + 1, beta1=opt_kw["beta1"],
-                                beta2=opt_kw["beta2"], eps=opt_kw["epsilon"], weight_decay=0.0,
-                                adamw=False)
+                                beta2=opt_kw["beta2"], eps=opt_kw["epsilon"],
+                                **(decay.adam_kw if decay
+                                   else dict(weight_decay=0.0, adamw=False)))
                 else:
-                    optim.sgd_(model.flat.data, g, lr)
+                    optim.sgd_(model.flat.data, g, lr, **(decay.sgd_kw if decay else {}))
             return float(loss), float(acc)
 
     # one name tuple per slot plane, kernels in TF layout like the variables themselves

@@ -44,6 +44,9 @@ def train_model_mirrored(flags, log=print):
     from ..ops import dropout
 
     dropout.refuse(flags, "--model %s" % flags.model)
+    from ..ops import weight_decay
+
+    weight_decay.refuse(flags, "--model %s (it has its own weight decay)" % flags.model)
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))

@@ -145,6 +145,10 @@ class Worker:
         from ..ops import dropout
 
         dropout.refuse(flags, "--strategy ps_async")
+        # --weight_decay / --nesterov: the parameter store's apply kernels have neither
+        from ..ops import weight_decay
+
+        weight_decay.refuse(flags, "--strategy ps_async (--ps_device cpu and gpu)")
         if device is None or device == "auto":
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)

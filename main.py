@@ -94,6 +94,19 @@ def main(argv=None):
             dropout.check_rate(FLAGS.dropout)
     except ValueError as e:
         raise SystemExit(str(e))
+    # --weight_decay / --adamw / --nesterov: the mirrored MLP's update only (ops/weight_decay.py)
+    from distributedtensorflowexample_amd.ops import weight_decay
+
+    try:
+        if FLAGS.strategy != "mirrored":
+            weight_decay.refuse(FLAGS, "--strategy ps_async (--ps_device cpu and gpu)")
+        elif FLAGS.model != "mlp":
+            weight_decay.refuse(FLAGS, "--model %s (it has its own weight decay)" % FLAGS.model)
+        elif getattr(FLAGS, "zero1", False):
+            weight_decay.refuse(FLAGS, "--zero1 (the sharded update)")
+        weight_decay.from_flags(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if FLAGS.strategy == "mirrored" and FLAGS.model != "mlp":
         from distributedtensorflowexample_amd.train.mirrored_mlp import shutdown_mirrored
         from distributedtensorflowexample_amd.train.mirrored_models import train_model_mirrored
