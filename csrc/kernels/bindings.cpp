@@ -62,27 +62,37 @@ PYBIND11_MODULE(_hip, m) {
   }, py::arg("p_old"), py::arg("grad"), py::arg("lr"), py::arg("p_new"), py::arg("x"),
      py::arg("ws"), py::arg("B"), py::arg("stream"), py::arg("trace") = 0);
   m.def("mlp_head", [](uintptr_t p_old, uintptr_t grad, float lr, uintptr_t p_new, uintptr_t lab,
-                       uintptr_t ws, int B, uintptr_t s, uintptr_t tr) {
+                       uintptr_t ws, int B, uintptr_t s, uintptr_t tr, int act) {
     dtfx::mlp_head_launch(P<const float>(p_old), P<const float>(grad), lr, P<float>(p_new),
-                          P<const int>(lab), P<float>(ws), B, S(s), P<unsigned long long>(tr));
+                          P<const int>(lab), P<float>(ws), B, S(s), P<unsigned long long>(tr),
+                          nullptr, act);
   }, py::arg("p_old"), py::arg("grad"), py::arg("lr"), py::arg("p_new"), py::arg("labels"),
-     py::arg("ws"), py::arg("B"), py::arg("stream"), py::arg("trace") = 0);
+     py::arg("ws"), py::arg("B"), py::arg("stream"), py::arg("trace") = 0, py::arg("act") = 0);
   // Hidden-layer dropout (ops/dropout.py): the heads' DROP forms.  ctr: the device global_step
   // counter; k0 / k1: the seed's words; thr, scale: dropout.threshold(rate); rank: the stream.
+  // act (here and in mlp_head / mlp_lean_head / mlp_eval / the plans' set_act): the hidden
+  // activation's id, ops/hidden_act.py (0 sigmoid, 1 relu, 2 tanh).
   m.def("mlp_head_drop", [](uintptr_t p_old, uintptr_t grad, float lr, uintptr_t p_new,
                             uintptr_t lab, uintptr_t ws, int B, uintptr_t s, uintptr_t ctr,
-                            unsigned k0, unsigned k1, unsigned thr, unsigned rank, float scale) {
+                            unsigned k0, unsigned k1, unsigned thr, unsigned rank, float scale,
+                            int act) {
     const dtfx::MlpDrop d{P<const int>(ctr), k0, k1, thr, rank, scale};
     dtfx::mlp_head_launch(P<const float>(p_old), P<const float>(grad), lr, P<float>(p_new),
-                          P<const int>(lab), P<float>(ws), B, S(s), nullptr, &d);
-  }, "mlp_head with inverted dropout on the hidden activation (mask: Philox of seed, *ctr, "
+                          P<const int>(lab), P<float>(ws), B, S(s), nullptr, &d, act);
+  }, py::arg("p_old"), py::arg("grad"), py::arg("lr"), py::arg("p_new"), py::arg("labels"),
+     py::arg("ws"), py::arg("B"), py::arg("stream"), py::arg("ctr"), py::arg("k0"), py::arg("k1"),
+     py::arg("thr"), py::arg("rank"), py::arg("scale"), py::arg("act") = 0,
+     "mlp_head with inverted dropout on the hidden activation (mask: Philox of seed, *ctr, "
      "rank, row, unit)");
   m.def("mlp_lean_head_drop", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s,
                                  uintptr_t ctr, unsigned k0, unsigned k1, unsigned thr,
-                                 unsigned rank, float scale) {
+                                 unsigned rank, float scale, int act) {
     const dtfx::MlpDrop d{P<const int>(ctr), k0, k1, thr, rank, scale};
-    dtfx::mlp_lean_head_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s), &d);
-  }, "mlp_lean_head with inverted dropout on the hidden activation");
+    dtfx::mlp_lean_head_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s), &d,
+                               act);
+  }, py::arg("p"), py::arg("labels"), py::arg("ws"), py::arg("B"), py::arg("stream"),
+     py::arg("ctr"), py::arg("k0"), py::arg("k1"), py::arg("thr"), py::arg("rank"),
+     py::arg("scale"), py::arg("act") = 0, "mlp_lean_head with inverted dropout on the hidden activation");
   m.def("mlp_wgrad", [](uintptr_t p, float lr, uintptr_t grad, uintptr_t x, uintptr_t ws,
                         uintptr_t ctr, uintptr_t stats, int ring, int B, uintptr_t s,
                         uintptr_t tr) {
@@ -129,9 +139,12 @@ PYBIND11_MODULE(_hip, m) {
      "first launch of the single-GPU two-launch step: the lean kernel (packed, preloaded kernel "
      "arguments; the same results as mlp_fwdapply(ks=28)); with DTFX_MLP_KS=14 the 14-slice "
      "mlp_fwdapply");
-  m.def("mlp_lean_head", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s) {
-    dtfx::mlp_lean_head_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s));
+  m.def("mlp_lean_head", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s,
+                            int act) {
+    dtfx::mlp_lean_head_launch(P<const float>(p), P<const int>(lab), P<float>(ws), B, S(s),
+                               nullptr, act);
   }, py::arg("p"), py::arg("labels"), py::arg("ws"), py::arg("B"), py::arg("stream"),
+     py::arg("act") = 0,
      "head of the single-GPU two-launch step after mlp_lean_fwdapply: row-major factors out, as "
      "mlp_head2(single=1)");
   m.def("mlp_head2", [](uintptr_t p, uintptr_t lab, uintptr_t ws, int B, uintptr_t s, int nslab,
@@ -160,15 +173,15 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mlp_run_pipelined", [](uintptr_t p0, uintptr_t p1, int cur, int pending, float lr,
                                 uintptr_t x, uintptr_t lab, int nbatches, int pos, int n,
                                 uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B,
-                                uintptr_t s, int flush) {
+                                uintptr_t s, int flush, int act) {
     py::gil_scoped_release nogil;
     dtfx::mlp_run_pipelined_launch(P<float>(p0), P<float>(p1), cur, pending, lr, P<const float>(x),
                                    P<const int>(lab), nbatches, pos, n, P<float>(ws), P<int>(ctr),
-                                   P<float>(stats), ring, B, S(s), flush);
+                                   P<float>(stats), ring, B, S(s), flush, nullptr, act);
   }, py::arg("p0"), py::arg("p1"), py::arg("cur"), py::arg("pending"), py::arg("lr"), py::arg("x"),
      py::arg("labels"), py::arg("nbatches"), py::arg("pos"), py::arg("n"), py::arg("ws"),
      py::arg("ctr"), py::arg("stats"), py::arg("ring"), py::arg("B"), py::arg("stream"),
-     py::arg("flush") = 0);
+     py::arg("flush") = 0, py::arg("act") = 0);
   m.def("mlp_set_flush_fused", &dtfx::mlp_set_flush_fused,
         "run_launched(.., flush=True): 1 = the last step's head and the flush in one launch "
         "(mlp_head_flush_kernel; opt-in, measured slower), 0 = the flush as its own launch; "
@@ -192,6 +205,8 @@ PYBIND11_MODULE(_hip, m) {
       drop = dtfx::MlpDrop{ctr, k0, k1, thr, rank, scale};
       has_drop = true;
     }
+    int act = 0;  // set_act: the hidden activation of every head of the loop
+    void set_act(int a) { act = a; }
   };
   static const auto bound = [](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
                                uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B) {
@@ -205,10 +220,12 @@ PYBIND11_MODULE(_hip, m) {
         py::gil_scoped_release nogil;
         dtfx::mlp_run_pipelined_launch(p.p0, p.p1, cur, pending, lr, p.x, p.labels, p.nbatches,
                                        pos, n, p.ws, p.ctr, p.stats, p.ring, p.B, S(s), flush,
-                                       p.dropp());
+                                       p.dropp(), p.act);
       }, "(cur, pending, lr, pos, n, flush, stream): mlp_run_pipelined with the bound buffers")
       .def("set_drop", &MlpRunPlan::set_drop,
-           "(k0, k1, thr, rank, scale): hidden-layer dropout in every head of the loop");
+           "(k0, k1, thr, rank, scale): hidden-layer dropout in every head of the loop")
+      .def("set_act", &MlpRunPlan::set_act,
+           "(act): the hidden activation of every head of the loop (0 sigmoid, 1 relu, 2 tanh)");
   m.def("mlp_apply", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev, uintptr_t ws,
                         uintptr_t ctr, uintptr_t stats, int ring, int B, uintptr_t s) {
     dtfx::mlp_apply_launch(P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev),
@@ -336,12 +353,14 @@ PYBIND11_MODULE(_hip, m) {
         py::gil_scoped_release nogil;
         dtfx::mlp_run_pipelined_opt_launch(p.p0, p.p1, cur, pending, lr, p.x, p.labels,
                                            p.nbatches, pos, n, p.ws, p.ctr, p.stats, p.ring, p.B,
-                                           S(s), flush, p.opt, p.dropp());
+                                           S(s), flush, p.opt, p.dropp(), p.act);
       }, "(cur, pending, lr, pos, n, flush, stream): the C++ host loop of the two-launch step "
          "with momentum / adam over the bound buffers (MlpRunPlan's call)")
       .def("set_drop", [](MlpRunOptPlan& p, unsigned k0, unsigned k1, unsigned thr, unsigned rank,
                           float scale) { p.set_drop(k0, k1, thr, rank, scale); },
-           "(k0, k1, thr, rank, scale): hidden-layer dropout in every head of the loop");
+           "(k0, k1, thr, rank, scale): hidden-layer dropout in every head of the loop")
+      .def("set_act", [](MlpRunOptPlan& p, int a) { p.set_act(a); },
+           "(act): the hidden activation of every head of the loop (0 sigmoid, 1 relu, 2 tanh)");
   m.def("mlp_persistent_ll_words", &dtfx::mlp_persistent_ll_words);
   m.def("mlp_persistent_blocks", &dtfx::mlp_persistent_blocks);
   m.def("mlp_persistent_trace_steps", &dtfx::mlp_persistent_trace_steps);
@@ -421,11 +440,11 @@ PYBIND11_MODULE(_hip, m) {
      "per-epoch reshuffle gather: dst[w][j] = src[w][perm(seed, epoch, n)[j]] over `planes` "
      "planes of [n, 784] f32 (strides in floats) and the int32 labels (csrc/kernels/shuffle.hip)");
   m.def("mlp_eval", [](uintptr_t p, uintptr_t x, uintptr_t lab, int n, uintptr_t acc,
-                        uintptr_t pred, uintptr_t probs, uintptr_t s) {
+                        uintptr_t pred, uintptr_t probs, uintptr_t s, int act) {
     dtfx::mlp_eval_launch(P<const float>(p), P<const float>(x), P<const int>(lab), n, P<void>(acc),
-                          P<int>(pred), P<float>(probs), S(s));
+                          P<int>(pred), P<float>(probs), S(s), act);
   }, py::arg("p"), py::arg("x"), py::arg("labels"), py::arg("n"), py::arg("acc"), py::arg("pred"),
-     py::arg("probs"), py::arg("stream"),
+     py::arg("probs"), py::arg("stream"), py::arg("act") = 0,
      "fused evaluation of the 784-100-10 MLP on n rows (csrc/kernels/mlp_eval.hip): pred int32 "
      "[n] / probs f32 [n, 10] optional (0); labels 0: predict only, acc untouched; otherwise acc "
      "(mlp_eval_acc_bytes bytes) is zeroed on the stream and then accumulated");

@@ -30,6 +30,33 @@ __device__ __forceinline__ float sigmoidf_(float z) {
   return z >= 0.f ? r : e * r;
 }
 
+// Hidden activations of the MNIST MLP (ops/hidden_act.py has the definition and these ids).
+enum : int { HACT_SIGMOID = 0, HACT_RELU = 1, HACT_TANH = 2 };
+
+__device__ __forceinline__ float tanhf_(float z) {
+  // sigmoidf_'s shape: exp of a non-positive argument, v_rcp_f32, the sign restored by bits
+  // (saturates at +-1, branch-free, no library call).  Near 0 the error is absolute, ~1e-7.
+  const float e = __expf(-2.f * fabsf(z));
+  const float t = (1.f - e) * __builtin_amdgcn_rcpf(1.f + e);
+  return copysignf(t, z);
+}
+
+// h(z), and the derivative as a factor on the incoming gradient, from h alone: sigmoid
+// h (1 - h), tanh 1 - h^2, ReLU [h > 0] (0 at z == 0; a select, so -0 and NaN give +0).
+template <int ACT>
+__device__ __forceinline__ float hidden_act(float z) {
+  static_assert(ACT == HACT_SIGMOID || ACT == HACT_RELU || ACT == HACT_TANH, "unknown activation");
+  if constexpr (ACT == HACT_RELU) return z > 0.f ? z : 0.f;
+  else if constexpr (ACT == HACT_TANH) return tanhf_(z);
+  else return sigmoidf_(z);
+}
+template <int ACT>
+__device__ __forceinline__ float hidden_act_bwd(float dh, float h) {
+  if constexpr (ACT == HACT_RELU) return h > 0.f ? dh : 0.f;
+  else if constexpr (ACT == HACT_TANH) return dh * (1.f - h * h);
+  else return dh * h * (1.f - h);
+}
+
 // DPP wave reductions (VALU lane moves, no LDS round trip as __shfl_xor's
 // ds_bpermute needs): quad_perm xor1/xor2, row_ror 4/8 -> every lane holds its
 // 16-lane row sum; row_bcast15/31 fold rows into lane 63; readlane -> SGPR.

@@ -3,7 +3,10 @@
 // self.net), the summed softmax cross-entropy, the number of correct rows and a 10 x 10
 // confusion matrix.  Reference: worker.py:87-90,150-154 (the 10,000-image test accuracy).
 //
-//   z1 = x . W1 + b1, h = sigmoid(z1), logits = h . W2 + b2, softmax, xent, arg-max
+//   z1 = x . W1 + b1, h = act(z1), logits = h . W2 + b2, softmax, xent, arg-max
+//
+// act: sigmoid (the reference's), relu or tanh (ops/hidden_act.py; common.h: hidden_act<ACT>), one
+// instantiation each; the sigmoid one is the kernel as it was.
 //
 // h and the logits never reach global memory; every element of x is loaded exactly once, by
 // one lane.  All matrix work is v_mfma_f32_16x16x4_f32 (exact f32; lane layout and the
@@ -74,6 +77,7 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 namespace dtfx {
 namespace mlpeval {
@@ -144,6 +148,7 @@ __device__ __forceinline__ void store_chunk(float4* __restrict__ buf, int w, int
   }
 }
 
+template <int ACT>
 __global__ __launch_bounds__(NW * 64) void mlp_eval_kernel(
     const float* __restrict__ p, const float* __restrict__ x, const int* __restrict__ labels,
     int n, EvalAcc* __restrict__ acc, int* __restrict__ pred, float* __restrict__ probs) {
@@ -234,7 +239,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_eval_kernel(
     __syncthreads();
   }
 
-  // h = sigmoid(z1 + b1) from the C layout (lane: column r of tile jt, rows 4 q + i) into the
+  // h = act(z1 + b1) from the C layout (lane: column r of tile jt, rows 4 q + i) into the
   // wave's tile; padded hidden units are 0
   float* ht = hs[w];
 #pragma unroll
@@ -242,7 +247,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_eval_kernel(
     const bool cv = jt * 16 + r < H;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      ht[(q * 4 + i) * HS + jt * 16 + r] = cv ? sigmoidf_(z[jt][i] + b1v[jt]) : 0.f;
+      ht[(q * 4 + i) * HS + jt * 16 + r] = cv ? hidden_act<ACT>(z[jt][i] + b1v[jt]) : 0.f;
   }
   __syncthreads();
   // logits = h . W2: A[row r][k] from the tile, B from the registers requested at the start
@@ -325,8 +330,11 @@ int mlp_eval_row_tile() { return mlpeval::T; }
 int mlp_eval_max_rows() { return mlpeval::kMaxRows; }
 
 void mlp_eval_launch(const float* p, const float* x, const int* labels, int n, void* acc, int* pred,
-                     float* probs, hipStream_t stream) {
+                     float* probs, hipStream_t stream, int act) {
   using namespace mlpeval;
+  if (act != HACT_SIGMOID && act != HACT_RELU && act != HACT_TANH)
+    throw std::invalid_argument("mlp_eval: unknown hidden activation id " + std::to_string(act) +
+                                " (0 sigmoid, 1 relu, 2 tanh)");
   if (n < 0 || n > kMaxRows)
     throw std::invalid_argument("mlp_eval: n must be in [0, " + std::to_string(kMaxRows) +
                                 "] (the 64-bit fixed-point loss sum cannot overflow up to there)");
@@ -335,8 +343,13 @@ void mlp_eval_launch(const float* p, const float* x, const int* labels, int n, v
   if (labels != nullptr) DTFX_HIP_CHECK(hipMemsetAsync(acc, 0, sizeof(EvalAcc), stream));
   if (n == 0) return;
   const int grid = (n + T - 1) / T;
-  hipLaunchKernelGGL(mlp_eval_kernel, dim3(grid), dim3(NW * 64), 0, stream, p, x, labels, n,
-                     static_cast<EvalAcc*>(acc), pred, probs);
+  auto launch = [&](auto ACT) {
+    hipLaunchKernelGGL((mlp_eval_kernel<ACT()>), dim3(grid), dim3(NW * 64), 0, stream, p, x, labels,
+                       n, static_cast<EvalAcc*>(acc), pred, probs);
+  };
+  if (act == HACT_RELU) launch(std::integral_constant<int, HACT_RELU>{});
+  else if (act == HACT_TANH) launch(std::integral_constant<int, HACT_TANH>{});
+  else launch(std::integral_constant<int, HACT_SIGMOID>{});
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

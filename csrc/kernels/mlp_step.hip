@@ -196,9 +196,23 @@ static void check_drop(const MlpDrop& d, const char* who) {
   if (bad) throw std::runtime_error(std::string(who) + bad);
 }
 
+// The hidden activation (common.h: HACT_*; ops/hidden_act.py) as a compile-time constant; an id
+// outside the set throws.  The heads' relu / tanh instantiations are the plain and the dropout
+// form of the lean head and of the three-launch head: nothing else has a variant.
+template <class F>
+static inline void with_act(int act, const char* who, F&& f) {
+  if (act == HACT_SIGMOID) f(std::integral_constant<int, HACT_SIGMOID>{});
+  else if (act == HACT_RELU) f(std::integral_constant<int, HACT_RELU>{});
+  else if (act == HACT_TANH) f(std::integral_constant<int, HACT_TANH>{});
+  else
+    throw std::runtime_error(std::string(who) + ": unknown hidden activation id " +
+                             std::to_string(act) + " (0 sigmoid, 1 relu, 2 tanh)");
+}
+static void check_act(int act, const char* who) { with_act(act, who, [](auto) {}); }
+
 void mlp_head_launch(const float* p_old, const float* grad, float lr, float* p_new,
                      const int* labels, float* ws, int B, hipStream_t stream,
-                     unsigned long long* tr, const MlpDrop* drop) {
+                     unsigned long long* tr, const MlpDrop* drop, int act) {
   using namespace mlp;
   check_b(B);
   const Bufs w = make_bufs(ws, B);
@@ -207,11 +221,26 @@ void mlp_head_launch(const float* p_old, const float* grad, float lr, float* p_n
   if (drop) {
     check_drop(*drop, "mlp_head");
     if (tr) throw std::runtime_error("mlp_head: the trace launch has no dropout variant");
-    with_flag(grad != nullptr, [&](auto APPLY) {
-      hipLaunchKernelGGL((mlp_head_drop_kernel<APPLY()>), dim3(B), dim3(64), 0, stream, p_old,
-                         APPLY() ? grad : p_old, APPLY() ? lr : 0.f, APPLY() ? p_new : nullptr,
-                         labels, w, B, drop->ctr, drop->k0, drop->k1, drop->thr, drop->stream,
-                         drop->scale);
+    with_act(act, "mlp_head", [&](auto ACT) {
+      with_flag(grad != nullptr, [&](auto APPLY) {
+        hipLaunchKernelGGL((mlp_head_drop_kernel<APPLY(), ACT()>), dim3(B), dim3(64), 0, stream,
+                           p_old, APPLY() ? grad : p_old, APPLY() ? lr : 0.f,
+                           APPLY() ? p_new : nullptr, labels, w, B, drop->ctr, drop->k0, drop->k1,
+                           drop->thr, drop->stream, drop->scale);
+      });
+    });
+    DTFX_HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (act != HACT_SIGMOID) {
+    if (tr) throw std::runtime_error("mlp_head: the trace launch has no relu / tanh variant");
+    with_act(act, "mlp_head", [&](auto ACT) {
+      with_flag(grad != nullptr, [&](auto APPLY) {
+        hipLaunchKernelGGL((mlp_head_kernel<APPLY(), false, 0, KS, false, ACT()>), dim3(B),
+                           dim3(64), 0, stream, p_old, APPLY() ? grad : p_old,
+                           APPLY() ? lr : 0.f, APPLY() ? p_new : nullptr, labels, w, B, nullptr,
+                           MlpXg{}, nullptr);
+      });
     });
     DTFX_HIP_CHECK(hipGetLastError());
     return;
@@ -345,16 +374,19 @@ static void lean_first_launch(const float* p_old, float* p_new, float lr, const 
 }
 
 static void lean_head_launch(const float* p, const int* labels, float* ws, int B,
-                             hipStream_t stream, const MlpDrop* drop = nullptr) {
+                             hipStream_t stream, const MlpDrop* drop = nullptr,
+                             int act = HACT_SIGMOID) {
   using namespace mlp;
-  with_ngt(B, [&](auto NGT) {
-    if (drop)
-      hipLaunchKernelGGL((mlp_lean_head_drop_kernel<NGT()>), dim3(B), dim3(64), 0, stream, p,
-                         labels, ws, B, drop->ctr, drop->k0, drop->k1, drop->thr, drop->stream,
-                         drop->scale);
-    else
-      hipLaunchKernelGGL((mlp_lean_head_kernel<NGT()>), dim3(B), dim3(64), 0, stream, p, labels,
-                         ws, B);
+  with_act(act, "mlp_lean_head", [&](auto ACT) {
+    with_ngt(B, [&](auto NGT) {
+      if (drop)
+        hipLaunchKernelGGL((mlp_lean_head_drop_kernel<NGT(), ACT()>), dim3(B), dim3(64), 0, stream,
+                           p, labels, ws, B, drop->ctr, drop->k0, drop->k1, drop->thr,
+                           drop->stream, drop->scale);
+      else
+        hipLaunchKernelGGL((mlp_lean_head_kernel<NGT(), ACT()>), dim3(B), dim3(64), 0, stream, p,
+                           labels, ws, B);
+    });
   });
 }
 
@@ -400,16 +432,19 @@ void mlp_lean_fwdapply_launch(const float* p_old, float* p_new, float lr, const 
 
 // Its head (row-major factors out); DTFX_MLP_KS=14: mlp_head2_launch.
 void mlp_lean_head_launch(const float* p, const int* labels, float* ws, int B,
-                          hipStream_t stream, const MlpDrop* drop) {
+                          hipStream_t stream, const MlpDrop* drop, int act) {
   if (drop) {
     check_drop(*drop, "mlp_lean_head");
     if (mlp_single_ks() != mlp::KS3)
       throw std::runtime_error("mlp_lean_head: DTFX_MLP_KS=14 has no dropout variant");
   }
+  check_act(act, "mlp_lean_head");
+  if (act != HACT_SIGMOID && mlp_single_ks() != mlp::KS3)
+    throw std::runtime_error("mlp_lean_head: DTFX_MLP_KS=14 has no relu / tanh variant");
   if (mlp_single_ks() != mlp::KS3) return mlp_head2_launch(p, labels, ws, B, stream, mlp::KS2);
   check_b(B);
   if (!p || !labels || !ws) throw std::runtime_error("mlp_lean_head: null buffer");
-  lean_head_launch(p, labels, ws, B, stream, drop);
+  lean_head_launch(p, labels, ws, B, stream, drop, act);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
@@ -743,9 +778,17 @@ static void run_pipelined(float* p0, float* p1, int cur, int pending, const floa
 void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float lr,
                               const float* x, const int* labels, int nbatches, int pos, int n,
                               float* ws, int* ctr, float* stats, int stats_ring, int B,
-                              hipStream_t stream, int flush, const MlpDrop* drop) {
+                              hipStream_t stream, int flush, const MlpDrop* drop, int act) {
   using namespace mlp;
   check_b(B);
+  check_act(act, "mlp_run_pipelined");
+  if (act != HACT_SIGMOID) {
+    if (mlp_single_ks() != KS3)
+      throw std::runtime_error("mlp_run_pipelined: DTFX_MLP_KS=14 has no relu / tanh variant");
+    if (flush && mlp_flush_fused())
+      throw std::runtime_error(
+          "mlp_run_pipelined: the fused flush (DTFX_MLP_FLUSH_FUSED) has no relu / tanh variant");
+  }
   if (drop) {
     check_drop(*drop, "mlp_run_pipelined");
     if (mlp_single_ks() != KS3)
@@ -769,7 +812,7 @@ void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float 
       if constexpr (KSV() == KS3) {
         lean_first_launch<true>(po, pn, pend ? lr : 0.f, xprev, xcur, ws, ctr, stats, stats_ring, B,
                                 pend, stream);
-        lean_head_launch(pn, lab, ws, B, stream, drop);
+        lean_head_launch(pn, lab, ws, B, stream, drop, act);
       } else {
         first(po, pn, xprev, xcur, pend);
         head_plain_launch<KSV()>(pn, lab, w, B, stream);
@@ -801,9 +844,10 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
                                   const float* x, const int* labels, int nbatches, int pos, int n,
                                   float* ws, int* ctr, float* stats, int stats_ring, int B,
                                   hipStream_t stream, int flush, const MlpOpt& o,
-                                  const MlpDrop* drop) {
+                                  const MlpDrop* drop, int act) {
   check_b(B);
   check_opt(o, "mlp_run_pipelined_opt");
+  check_act(act, "mlp_run_pipelined_opt");
   if (drop) check_drop(*drop, "mlp_run_pipelined_opt");
   if (!p0 || !p1 || p0 == p1 || !x || !labels || !ctr || !ws || nbatches < 1 || pos < 0 ||
       pos >= nbatches || n < 0 || (cur != 0 && cur != 1))
@@ -818,7 +862,7 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
                   const int* lab, int pend, int par) {
     lean_first_opt_launch<true>(po, pn, lr, xprev, xcur, ws, ctr, stats, stats_ring, B, pend, par,
                                 o, stream);
-    lean_head_launch(pn, lab, ws, B, stream, drop);
+    lean_head_launch(pn, lab, ws, B, stream, drop, act);
   };
   auto apply = [&](const float* po, float* pn, const float* xprev, int par) {
     lean_first_opt_launch<false>(po, pn, lr, xprev, xprev, ws, ctr, stats, stats_ring, B, 1, par, o,

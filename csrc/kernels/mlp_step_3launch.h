@@ -157,9 +157,13 @@ __global__ __launch_bounds__(64) void mlp_fwd_kernel(
 // loads' waits (DTFX_MLP_DROP_PLACE above: pinned ahead of the first slab use it measured no
 // faster).  hbuf and the logits take the dropped, rescaled h; dz1 the mask factor
 // and the undropped h.  DROP = false compiles to the code without it.
+// ACT (common.h: hidden_act / hidden_act_bwd): the hidden activation.  Its derivative comes from
+// the h the lane already holds, so ReLU and tanh add no load, no launch and no workspace; ReLU's
+// h is a select (exactly +0 for z <= 0, padding lanes too).  HACT_SIGMOID compiles to the code
+// before the parameter existed.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false, int NGT = 0,
-          bool SB = false, bool DROP = false>
+          bool SB = false, bool DROP = false, int ACT = HACT_SIGMOID>
 __device__ __forceinline__ void head_row(
     const int row, const int lane, const float* __restrict__ p_old,
     const float* __restrict__ grad, float lr, float* __restrict__ p_new,
@@ -167,6 +171,8 @@ __device__ __forceinline__ void head_row(
     const MlpXg& xg, float* __restrict__ dz1A, const MlpDrop& da = MlpDrop{}) {
   static_assert(XW == 0 || (!APPLY && !TRACE), "the factor exchange runs the direct step");
   static_assert(!DROP || (XW == 0 && !TRACE), "dropout: the lean head and the three-launch head");
+  static_assert(ACT == HACT_SIGMOID || (XW == 0 && !TRACE),
+                "relu / tanh: the lean head and the three-launch head");
   static_assert(!RM || (XW == 0 && !APPLY), "row-major factors: the single-GPU two-launch step");
   static_assert(!SB || (RM && NSLAB == KS3), "slab loads through a descriptor: the lean head");
   if (TRACE) trace_stamp(tr, row * 4 + 0);
@@ -300,7 +306,7 @@ __device__ __forceinline__ void head_row(
   float hd[2];  // what the logits and hbuf take: h, or with DROP the dropped, rescaled h
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const float sg = sigmoidf_(zs[u] + b1v[u]);
+    const float sg = hidden_act<ACT>(zs[u] + b1v[u]);
     hv[u] = pv ? sg : 0.f;
     if constexpr (DROP) hd[u] = hv[u] * mf[u];
     else hd[u] = hv[u];
@@ -343,7 +349,7 @@ __device__ __forceinline__ void head_row(
 #pragma unroll
       for (int c = 0; c < C; ++c) dh += dl[c] * w2[u][c];
       if constexpr (DROP) dh *= mf[u];
-      dzv[u] = dh * hv[u] * (1.f - hv[u]);
+      dzv[u] = hidden_act_bwd<ACT>(dh, hv[u]);
       if (!RM) w.dz1T[(size_t)j * BP + row] = dzv[u];
     }
   }
@@ -369,28 +375,29 @@ __device__ __forceinline__ void head_row(
   if (TRACE) trace_stamp(tr, row * 4 + 3);
 }
 
-template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false>
+template <bool APPLY, bool TRACE, int XW = 0, int NSLAB = KS, bool RM = false,
+          int ACT = HACT_SIGMOID>
 __global__ __launch_bounds__(64) void mlp_head_kernel(
     const float* __restrict__ p_old, const float* __restrict__ grad, float lr,
     float* __restrict__ p_new, const int* __restrict__ labels, Bufs w, int B,
     unsigned long long* __restrict__ tr, MlpXg xg, float* __restrict__ dz1A) {
-  head_row<APPLY, TRACE, XW, NSLAB, RM>(blockIdx.x, threadIdx.x, p_old, grad, lr, p_new, labels, w,
-                                     B, tr, xg, dz1A);
+  head_row<APPLY, TRACE, XW, NSLAB, RM, 0, false, false, ACT>(
+      blockIdx.x, threadIdx.x, p_old, grad, lr, p_new, labels, w, B, tr, xg, dz1A);
 }
 
 // The three-launch head with dropout (the direct step, and the all-reduce engine's step_grad with
 // and without its deferred apply).  ctr apart: `const int* __restrict__`, so the step word is a
 // scalar load issued with the label's.
-template <bool APPLY>
+template <bool APPLY, int ACT = HACT_SIGMOID>
 __global__ __launch_bounds__(64) void mlp_head_drop_kernel(
     const float* __restrict__ p_old, const float* __restrict__ grad, float lr,
     float* __restrict__ p_new, const int* __restrict__ labels, Bufs w, int B,
     const int* __restrict__ ctr, unsigned k0, unsigned k1, unsigned thr, unsigned stream,
     float scale) {
   const MlpDrop da = {ctr, k0, k1, thr, stream, scale};
-  head_row<APPLY, false, 0, KS, false, 0, false, true>(blockIdx.x, threadIdx.x, p_old, grad, lr,
-                                                       p_new, labels, w, B, nullptr, MlpXg{},
-                                                       nullptr, da);
+  head_row<APPLY, false, 0, KS, false, 0, false, true, ACT>(blockIdx.x, threadIdx.x, p_old, grad,
+                                                            lr, p_new, labels, w, B, nullptr,
+                                                            MlpXg{}, nullptr, da);
 }
 
 // ---------------------------------------------------------------------------

@@ -22,6 +22,12 @@ struct MlpDrop {
   float scale;
 };
 
+// ---- the hidden activation of the step's head and of the evaluation kernel (ops/hidden_act.py
+// has the definition; the ids are common.h's HACT_*): 0 sigmoid, the reference's and every
+// launcher's default, 1 relu, 2 tanh.  Launchers throw on any other id, and where no relu / tanh
+// variant exists (DTFX_MLP_KS=14, the fused flush, the trace launches).
+constexpr int kMlpActSigmoid = 0;
+
 // ---- workspace / layout queries and knobs
 long long mlp_workspace_floats(int B);
 void mlp_rowmajor_layout(int B, long long* out);
@@ -38,7 +44,8 @@ void mlp_fwd_launch(const float* p_old, const float* grad, float lr, float* p_ne
                     float* ws, int B, hipStream_t stream, unsigned long long* tr);
 void mlp_head_launch(const float* p_old, const float* grad, float lr, float* p_new,
                      const int* labels, float* ws, int B, hipStream_t stream,
-                     unsigned long long* tr, const MlpDrop* drop = nullptr);
+                     unsigned long long* tr, const MlpDrop* drop = nullptr,
+                     int act = kMlpActSigmoid);
 void mlp_wgrad_launch(float* p, float lr, float* grad, const float* x, float* ws, int* ctr,
                       float* stats, int stats_ring, int B, hipStream_t stream,
                       unsigned long long* tr);
@@ -57,7 +64,7 @@ void mlp_lean_fwdapply_launch(const float* p_old, float* p_new, float lr, const 
                               const float* x, float* ws, int* ctr, float* stats, int stats_ring,
                               int B, int stats_on, hipStream_t stream);
 void mlp_lean_head_launch(const float* p, const int* labels, float* ws, int B, hipStream_t stream,
-                          const MlpDrop* drop = nullptr);
+                          const MlpDrop* drop = nullptr, int act = kMlpActSigmoid);
 void mlp_pipelined_trace_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                                 const float* x, const int* labels, float* ws, int* ctr,
                                 float* stats, int stats_ring, int B, hipStream_t stream,
@@ -66,7 +73,7 @@ void mlp_pipelined_trace_launch(const float* p_old, float* p_new, float lr, cons
 void mlp_run_pipelined_launch(float* p0, float* p1, int cur, int pending, float lr, const float* x,
                               const int* labels, int nbatches, int pos, int n, float* ws, int* ctr,
                               float* stats, int stats_ring, int B, hipStream_t stream, int flush,
-                              const MlpDrop* drop = nullptr);
+                              const MlpDrop* drop = nullptr, int act = kMlpActSigmoid);
 
 // ---- momentum / Adam / learning-rate schedules inside the lean two-launch step.  kind: 1
 // momentum, 2 adam; s0 / s1: the slot planes; tp: the int32[2] step pair; h0..h2:
@@ -97,7 +104,7 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
                                   const float* x, const int* labels, int nbatches, int pos, int n,
                                   float* ws, int* ctr, float* stats, int stats_ring, int B,
                                   hipStream_t stream, int flush, const MlpOpt& o,
-                                  const MlpDrop* drop = nullptr);
+                                  const MlpDrop* drop = nullptr, int act = kMlpActSigmoid);
 void mlp_lr_sched_launch(const int* ctr, const int* blk, float lr0, float* out, float* lrs,
                          int ring, hipStream_t stream);
 
@@ -149,6 +156,6 @@ int mlp_eval_acc_bytes();
 int mlp_eval_row_tile();
 int mlp_eval_max_rows();
 void mlp_eval_launch(const float* p, const float* x, const int* labels, int n, void* acc, int* pred,
-                     float* probs, hipStream_t stream);
+                     float* probs, hipStream_t stream, int act = kMlpActSigmoid);
 
 }  // namespace dtfx

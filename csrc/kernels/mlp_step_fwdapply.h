@@ -607,34 +607,35 @@ __global__ __launch_bounds__(256) void mlp_lean_fwdapply_trace_kernel(
   lean_fwdapply_body<NGT, true, true>(p_old, p_new, x_prev, x, ws, ctr, stats, lr, flags, tr, trs);
 }
 
-template <int NGT, bool TRACE>
+template <int NGT, bool TRACE, int ACT = HACT_SIGMOID>
 __device__ __forceinline__ void lean_head_body(const float* __restrict__ p,
                                                const int* __restrict__ labels,
                                                float* __restrict__ ws, int B,
                                                unsigned long long* __restrict__ tr) {
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
-  head_row<false, TRACE, 0, KS3, true, NGT, true>(blockIdx.x, threadIdx.x, p, p, 0.f, nullptr,
-                                                  labels, w, B, tr, MlpXg{}, nullptr);
+  head_row<false, TRACE, 0, KS3, true, NGT, true, false, ACT>(
+      blockIdx.x, threadIdx.x, p, p, 0.f, nullptr, labels, w, B, tr, MlpXg{}, nullptr);
 }
 
-template <int NGT>
+// (ACT: the hidden activation, common.h; relu and tanh exist for the plain and the dropout head)
+template <int NGT, int ACT = HACT_SIGMOID>
 __global__ __launch_bounds__(64) void mlp_lean_head_kernel(const float* __restrict__ p,
                                                            const int* __restrict__ labels,
                                                            float* __restrict__ ws, int B) {
-  lean_head_body<NGT, false>(p, labels, ws, B, nullptr);
+  lean_head_body<NGT, false, ACT>(p, labels, ws, B, nullptr);
 }
 
 // The lean head with dropout (MlpDrop by its words: 14 argument dwords, all preloaded).
-template <int NGT>
+template <int NGT, int ACT = HACT_SIGMOID>
 __global__ __launch_bounds__(64) void mlp_lean_head_drop_kernel(
     const float* __restrict__ p, const int* __restrict__ labels, float* __restrict__ ws, int B,
     const int* __restrict__ ctr, unsigned k0, unsigned k1, unsigned thr, unsigned stream,
     float scale) {
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
   const MlpDrop da = {ctr, k0, k1, thr, stream, scale};
-  head_row<false, false, 0, KS3, true, NGT, true, true>(blockIdx.x, threadIdx.x, p, p, 0.f,
-                                                        nullptr, labels, w, B, nullptr, MlpXg{},
-                                                        nullptr, da);
+  head_row<false, false, 0, KS3, true, NGT, true, true, ACT>(blockIdx.x, threadIdx.x, p, p, 0.f,
+                                                             nullptr, labels, w, B, nullptr,
+                                                             MlpXg{}, nullptr, da);
 }
 
 template <int NGT>

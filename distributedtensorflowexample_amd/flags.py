@@ -266,8 +266,15 @@ def define_reference_flags(flag_values=FLAGS):
                   "async PS: mlp | softmax (softmax regression)", fv)
     DEFINE_string("hidden_units", "", "async PS, --model mlp: hidden layer widths, e.g. 256,128 "
                   "(default: the reference's 100)", fv)
-    DEFINE_string("activation", "sigmoid", "async PS, --model mlp: hidden activation "
-                  "(sigmoid | relu)", fv)
+    DEFINE_string("activation", "sigmoid",
+                  "--model mlp: the hidden activation, sigmoid (the reference's) | relu | tanh "
+                  "(ops/hidden_act.py).  --strategy mirrored: inside the fused step's head launch "
+                  "(one GPU), in the all-reduce engine (several) or on the autograd path "
+                  "(--device cpu), and in the periodic test evaluation.  --job_name eval: the "
+                  "activation the checkpoint is evaluated with; it must match the training run "
+                  "(a checkpoint does not record it).  --strategy ps_async: sigmoid | relu, the "
+                  "generic dense layers' epilogues (tanh is refused).  --model bert|resnet50 "
+                  "refuse a non-default value", fv)
     DEFINE_string("model_config", "base", "base | tiny (tiny = CPU-sized variant of bert/resnet50)",
                   fv)
     DEFINE_integer("seq_len", 128, "BERT sequence length", fv)

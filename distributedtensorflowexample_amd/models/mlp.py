@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 
 from ..ops import init as init_ops
-from ..ops import mlp_step, nn
+from ..ops import hidden_act, mlp_step, nn
 
 D, H, C = mlp_step.D, mlp_step.H, mlp_step.C
 
@@ -69,10 +69,13 @@ class MnistMLP(torch.nn.Module):
     Uses the fused-epilogue dense kernel and the fused softmax-xent kernel on
     the GPU; the same math in PyTorch on the CPU.  The flat buffer is shared
     with ``FusedMLPTrainer`` so both paths see the same parameters.
+    ``activation`` (``ops/hidden_act.py``): the hidden activation; sigmoid and relu are the dense
+    kernel's fused epilogues, tanh a linear dense layer followed by ``torch.tanh``.
     """
 
-    def __init__(self, device="cpu", seed=0, flat=None):
+    def __init__(self, device="cpu", seed=0, flat=None, activation="sigmoid"):
         super().__init__()
+        self.activation = hidden_act.check(activation)
         flat = init_params(device, seed) if flat is None else flat
         self.flat = torch.nn.Parameter(flat)
 
@@ -82,10 +85,17 @@ class MnistMLP(torch.nn.Module):
     def views(self):
         return mlp_step.unflatten(self.flat)
 
+    def hidden(self, x):
+        """The hidden activation h [B, 100] of ``x``."""
+        W1t, b1, _, _ = self.views()
+        if self.activation == "tanh":
+            return torch.tanh(nn.dense(x, W1t, b1, None))
+        return nn.dense(x, W1t, b1, self.activation)
+
     def forward(self, x):
         """Returns (softmax probabilities, logits) like build_net (worker.py:46-57)."""
         W1t, b1, W2t, b2 = self.views()
-        h = nn.dense(x, W1t, b1, "sigmoid")
+        h = self.hidden(x)
         logits = nn.dense(h, W2t, b2, None)
         return torch.softmax(logits, dim=-1), logits
 
@@ -97,6 +107,6 @@ class MnistMLP(torch.nn.Module):
             _, logits = self.forward(x)
             return nn.softmax_cross_entropy(logits, labels)
         W1t, b1, W2t, b2 = self.views()
-        h = nn.dense(x, W1t, b1, "sigmoid")
+        h = self.hidden(x)
         hd = h * (keep.to(h.device, h.dtype) * scale)
         return nn.softmax_cross_entropy(nn.dense(hd, W2t, b2, None), labels)

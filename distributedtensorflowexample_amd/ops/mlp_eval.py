@@ -15,12 +15,16 @@ Rows whose label is outside ``[0, 10)`` still get a prediction and probabilities
 counted in nothing (mask rows with ``-1``).  The arg-max is the lowest class whose logit
 equals the maximum (``tf.argmax``).  CPU tensors take the same function through
 ``mlp_step.reference_forward``.
+
+``activation=`` (``ops/hidden_act.py``: sigmoid, the reference's and the default, relu, tanh)
+selects the hidden activation on both paths: one kernel instantiation each.  A checkpoint does not
+record it, so the caller names the one the parameters were trained with.
 """
 from __future__ import annotations
 
 import torch
 
-from . import mlp_step
+from . import hidden_act, mlp_step
 from ._ext import hip, ptr, stream_handle
 
 D, H, C = mlp_step.D, mlp_step.H, mlp_step.C
@@ -116,8 +120,8 @@ def _check(params, x, labels, acc):
     return n
 
 
-def _evaluate_cpu(params, x, labels, predictions, probs, acc):
-    _, logits = mlp_step.reference_forward(params, x)
+def _evaluate_cpu(params, x, labels, predictions, probs, acc, activation="sigmoid"):
+    _, logits = mlp_step.reference_forward(params, x, activation)
     # lowest class whose logit equals the maximum (tf.argmax), whatever torch's tie rule
     m = logits.max(1, keepdim=True).values
     cls = torch.arange(C).expand_as(logits)
@@ -143,7 +147,8 @@ def _evaluate_cpu(params, x, labels, predictions, probs, acc):
     return EvalResult(acc, pred if predictions else None, out_probs)
 
 
-def evaluate(params, x, labels=None, *, predictions=False, probs=False, acc=None):
+def evaluate(params, x, labels=None, *, predictions=False, probs=False, acc=None,
+             activation="sigmoid"):
     """Evaluate the flat parameter buffer ``params`` on ``x`` [n, 784] (f32).
 
     ``labels`` (int32 [n]): loss, accuracy, counts and the confusion matrix are accumulated
@@ -151,17 +156,19 @@ def evaluate(params, x, labels=None, *, predictions=False, probs=False, acc=None
     written.  ``predictions`` / ``probs``: also return the predicted classes (int32 [n]) /
     the class probabilities (f32 [n, 10]).  ``acc``: reuse this accumulator block
     (:func:`new_acc`) instead of allocating one -- under graph capture, so that every replay
-    zeroes and fills the same block.
+    zeroes and fills the same block.  ``activation``: the model's hidden activation
+    (``sigmoid`` | ``relu`` | ``tanh``).
 
     GPU tensors: one memset node and one kernel on the current stream, no host
     synchronisation.  CPU tensors: the same result through ``mlp_step.reference_forward``.
     """
+    act = hidden_act.act_id(activation)
     n = _check(params, x, labels, acc)
     if labels is None:  # predict only: the accumulator (a caller's included) is not touched
         acc = None
         predictions = predictions or not probs
     if not x.is_cuda:
-        return _evaluate_cpu(params, x, labels, predictions, probs, acc)
+        return _evaluate_cpu(params, x, labels, predictions, probs, acc, activation)
     h = hip()
     if n > h.mlp_eval_max_rows():
         raise ValueError("mlp_eval: at most %d rows per call" % h.mlp_eval_max_rows())
@@ -171,7 +178,7 @@ def evaluate(params, x, labels=None, *, predictions=False, probs=False, acc=None
     pred = torch.empty(n, dtype=torch.int32, device=dev) if predictions else None
     pr = torch.empty(n, C, dtype=torch.float32, device=dev) if probs else None
     h.mlp_eval(ptr(params), ptr(x), ptr(labels), n, ptr(acc), ptr(pred), ptr(pr),
-               stream_handle(dev))
+               stream_handle(dev), act)
     return EvalResult(acc, pred, pr)
 
 

@@ -26,6 +26,7 @@ import os
 
 import torch
 
+from . import hidden_act
 from ._ext import hip, ptr, stream_handle
 
 D, H, C = 784, 100, 10
@@ -128,38 +129,45 @@ def _check_flat(*ts):
             raise ValueError("parameter/gradient buffers must be contiguous f32 [79510] on the GPU")
 
 
-def _head(h, p_old, grad, lr, p_new, labels, ws, s, dropout):
-    """The three-launch head, or with ``dropout`` (an ``ops.dropout.Dropout``) its DROP form."""
+def _head(h, p_old, grad, lr, p_new, labels, ws, s, dropout, activation="sigmoid"):
+    """The three-launch head, or with ``dropout`` (an ``ops.dropout.Dropout``) its DROP form;
+    ``activation`` (``ops/hidden_act.py``): sigmoid launches the kernels without the argument."""
+    act = hidden_act.act_id(activation)
     if dropout is None:
-        h.mlp_head(p_old, grad, lr, p_new, ptr(labels), ptr(ws.buf), ws.B, s)
+        h.mlp_head(p_old, grad, lr, p_new, ptr(labels), ptr(ws.buf), ws.B, s, 0, act)
     else:
         h.mlp_head_drop(p_old, grad, lr, p_new, ptr(labels), ptr(ws.buf), ws.B, s, ptr(ws.ctr),
-                        *dropout.args())
+                        *dropout.args(), act)
 
 
-def _lean_head(h, p, labels, ws, s, dropout):
-    """The lean head (row-major factors), or with ``dropout`` its DROP form."""
+def _lean_head(h, p, labels, ws, s, dropout, activation="sigmoid"):
+    """The lean head (row-major factors), or with ``dropout`` its DROP form; ``activation`` as
+    ``_head``."""
+    act = hidden_act.act_id(activation)
     if dropout is None:
-        h.mlp_lean_head(ptr(p), ptr(labels), ptr(ws.buf), ws.B, s)
+        h.mlp_lean_head(ptr(p), ptr(labels), ptr(ws.buf), ws.B, s, act)
     else:
         h.mlp_lean_head_drop(ptr(p), ptr(labels), ptr(ws.buf), ws.B, s, ptr(ws.ctr),
-                             *dropout.args())
+                             *dropout.args(), act)
 
 
-def step_direct(p, x, labels, ws: StepWorkspace, lr, stats=True, dropout=None):
+def step_direct(p, x, labels, ws: StepWorkspace, lr, stats=True, dropout=None,
+                activation="sigmoid"):
     """One full SGD step in place on ``p`` for the batch (x [B,784], labels [B]).
-    ``dropout``: an ``ops.dropout.Dropout`` (the mask of step ``ws.ctr``), or None."""
+    ``dropout``: an ``ops.dropout.Dropout`` (the mask of step ``ws.ctr``), or None.
+    ``activation``: the hidden activation, ``sigmoid`` | ``relu`` | ``tanh``
+    (``ops/hidden_act.py``); only the head launch differs."""
     _check(x, labels, ws.B)
     _check_flat(p)
     h, s = hip(), stream_handle()
     h.mlp_fwd(ptr(p), 0, 0.0, 0, ptr(x), ptr(ws.buf), ws.B, s)
-    _head(h, ptr(p), 0, 0.0, 0, labels, ws, s, dropout)
+    _head(h, ptr(p), 0, 0.0, 0, labels, ws, s, dropout, activation)
     h.mlp_wgrad(ptr(p), float(lr), 0, ptr(x), ptr(ws.buf), ptr(ws.ctr),
                 ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, s)
 
 
 def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, stats=True,
-                   dropout=None):
+                   dropout=None, activation="sigmoid"):
     """Two-launch single-GPU step: ``mlp_lean_fwdapply`` applies the PREVIOUS step's SGD update
     (from the factors dz1/h/dlogits the last head left in ``ws`` and the previous batch
     ``x_prev``; W1 never materialises a gradient) reading ``p_old`` and writing ``p_new``,
@@ -172,7 +180,9 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     last step's update stays pending until ``flush_pipelined``.
     ``dropout`` (an ``ops.dropout.Dropout``): the head drops hidden units by the mask of this
     step's global_step, which it reads from ``ws.ctr`` -- the first launch has just recorded the
-    step before, so the counter is this step's index."""
+    step before, so the counter is this step's index.
+    ``activation`` (``ops/hidden_act.py``): the head's hidden activation and its derivative; the
+    first launch and the flush are the same for every activation (they read the factors)."""
     _check(x, labels, ws.B)
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
@@ -182,7 +192,7 @@ def step_pipelined(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply
     h.mlp_lean_fwdapply(ptr(p_old), ptr(p_new), float(lr) if apply else 0.0,
                         ptr(x_prev if apply else x), ptr(x), ptr(ws.buf), ptr(ws.ctr),
                         ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, 1 if apply else 0, s)
-    _lean_head(h, p_new, labels, ws, s, dropout)  # (row-major factors)
+    _lean_head(h, p_new, labels, ws, s, dropout, activation)  # (row-major factors)
 
 
 def flush_pipelined(p_old, p_new, x_prev, ws: StepWorkspace, lr, stats=True):
@@ -268,12 +278,13 @@ class PipelinedOpt:
 
 
 def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, par,
-                       opt: PipelinedOpt, stats=True, dropout=None):
+                       opt: PipelinedOpt, stats=True, dropout=None, activation="sigmoid"):
     """``step_pipelined`` with momentum / Adam: the first launch applies the pending update to
     ``p_old -> p_new`` AND, in place, to ``opt.slots`` (Adam's ``t`` = ``opt.tp[par] + 1``).
     ``apply=False`` is an explicit bit here: a copy + forward that leaves every slot byte alone.
     ``par``: the index of ``p_old`` in the caller's ping-pong pair; consecutive launches
-    alternate it.  The head launch is ``step_pipelined``'s (``dropout`` too)."""
+    alternate it.  The head launch is ``step_pipelined``'s (``dropout`` and ``activation``
+    too)."""
     _check(x, labels, ws.B)
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
@@ -297,7 +308,7 @@ def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, a
         h.mlp_lean_fwdapply_opt(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
                                 ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
                                 ws.stats_ring, ws.B, 1 if apply else 0, int(par), *opt.args(), s)
-    _lean_head(h, p_new, labels, ws, s, dropout)
+    _lean_head(h, p_new, labels, ws, s, dropout, activation)
 
 
 def flush_pipelined_opt(p_old, p_new, x_prev, ws: StepWorkspace, lr, par, opt: PipelinedOpt,
@@ -429,12 +440,13 @@ def flush_factor(p, x_prev, ws: StepWorkspace, lr, comm, dz1A, xstride, stats=Tr
 
 
 def step_grad(p_old, x, labels, ws: StepWorkspace, grad, prev_grad=None, lr=0.0, p_new=None,
-              stats=True, dropout=None):
+              stats=True, dropout=None, activation="sigmoid"):
     """Forward/backward writing ``grad``; optionally first applies ``prev_grad``.
 
     With ``prev_grad`` the step computes on ``p_new = p_old - lr * prev_grad``
     (published into ``p_new`` by the kernels) -- the deferred apply of sync DP.
-    Returns the parameter buffer the gradient belongs to.  ``dropout``: as ``step_direct``.
+    Returns the parameter buffer the gradient belongs to.  ``dropout``, ``activation``: as
+    ``step_direct``.
     """
     _check(x, labels, ws.B)
     _check_flat(p_old, grad, prev_grad, p_new)
@@ -444,7 +456,7 @@ def step_grad(p_old, x, labels, ws: StepWorkspace, grad, prev_grad=None, lr=0.0,
     pg = ptr(prev_grad)
     pn = ptr(p_new) if prev_grad is not None else 0
     h.mlp_fwd(ptr(p_old), pg, float(lr), pn, ptr(x), ptr(ws.buf), ws.B, s)
-    _head(h, ptr(p_old), pg, float(lr), pn, labels, ws, s, dropout)
+    _head(h, ptr(p_old), pg, float(lr), pn, labels, ws, s, dropout, activation)
     h.mlp_wgrad(0, 0.0, ptr(grad), ptr(x), ptr(ws.buf), ptr(ws.ctr),
                 ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B, s)
     return p_new if prev_grad is not None else p_old
@@ -483,24 +495,31 @@ def from_tf_layout(tf, flat):
     return flat
 
 
-def reference_forward(p, x):
+def reference_forward(p, x, activation="sigmoid"):
     W1t, b1, W2t, b2 = unflatten(p)
-    h = torch.sigmoid(x @ W1t.t() + b1)
+    if hidden_act.check(activation) == "sigmoid":
+        h = torch.sigmoid(x @ W1t.t() + b1)
+    else:
+        h = hidden_act.forward(x @ W1t.t() + b1, activation)
     return h, h @ W2t.t() + b2
 
 
-def reference_step(p, x, labels):
-    """Plain-torch forward/backward of worker.py's graph: (grad, loss, accuracy)."""
+def reference_step(p, x, labels, activation="sigmoid"):
+    """Plain-torch forward/backward of worker.py's graph: (grad, loss, accuracy).
+    ``activation``: the hidden activation (``ops/hidden_act.py``; sigmoid is the reference's)."""
     W1t, b1, W2t, b2 = unflatten(p)
     B = x.shape[0]
-    h, logits = reference_forward(p, x)
+    h, logits = reference_forward(p, x, activation)
     lse = torch.logsumexp(logits, 1)
     lab = labels.long()
     loss = (lse - logits.gather(1, lab[:, None])[:, 0]).mean()
     acc = (logits.argmax(1) == lab).to(p.dtype).mean()
     prob = torch.softmax(logits, 1)
     dl = (prob - torch.nn.functional.one_hot(lab, C).to(p.dtype)) / B
-    dz = (dl @ W2t) * h * (1 - h)
+    if activation == "sigmoid":
+        dz = (dl @ W2t) * h * (1 - h)
+    else:
+        dz = (dl @ W2t) * hidden_act.derivative(h, activation)
     g = torch.empty_like(p)
     gW1t, gb1, gW2t, gb2 = unflatten(g)
     gW1t.copy_(dz.t() @ x)

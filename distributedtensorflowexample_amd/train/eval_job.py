@@ -1,7 +1,7 @@
 """``--job_name eval``: evaluate the latest checkpoint of a log directory on the test set.
 
     python main.py --job_name eval --logdir DIR [--data_dir ...] [--device auto|cuda|cpu]
-                   [--eval_output FILE.npy]
+                   [--eval_output FILE.npy] [--activation sigmoid|relu|tanh]
 
 No server and no process group is started.  The checkpoint (TF V2 bundle with the
 reference's variable names, train/saver.py) is restored into the flat parameter buffer and
@@ -9,6 +9,9 @@ run through ``ops.mlp_eval.evaluate``: the fused one-launch kernel on a GPU, the
 the same op with ``--device cpu`` (or on a machine without a GPU).  Prints the checkpoint's
 global step, the test accuracy, the test loss and the 10 x 10 confusion matrix
 ([label][predicted]); ``--eval_output`` saves the int32 predictions.
+
+``--activation`` is the model's hidden activation and must match the training run: a checkpoint
+keeps the reference's variable names and does not record it.
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import numpy as np
 import torch
 
 from ..data.mnist import read_test_set
-from ..ops import mlp_eval, mlp_step
+from ..ops import hidden_act, mlp_eval, mlp_step
 from .saver import latest_checkpoint, load_checkpoint
 from .worker import FUSED_TF_SHAPES, REFERENCE_MLP_NAMES, tf_vars_to_flat
 
@@ -47,6 +50,10 @@ def restore_flat(logdir):
 
 
 def eval_job(flags, log=print):
+    try:
+        act = hidden_act.from_flags(flags)
+    except ValueError as e:
+        raise SystemExit(str(e))
     flat, step, _ = restore_flat(flags.logdir)
     want = str(getattr(flags, "device", "auto") or "auto")
     if want == "auto":
@@ -56,8 +63,10 @@ def eval_job(flags, log=print):
     x = torch.from_numpy(np.ascontiguousarray(test.images, np.float32)).to(dev)
     y = torch.from_numpy(np.asarray(test.labels).astype(np.int32)).to(dev)
     out = str(getattr(flags, "eval_output", "") or "")
-    res = mlp_eval.evaluate(flat.to(dev), x, y, predictions=bool(out))
+    res = mlp_eval.evaluate(flat.to(dev), x, y, predictions=bool(out), activation=act)
     log("global_step: {}".format(step))
+    if act != hidden_act.DEFAULT:
+        log("activation: {}".format(act))
     log("test accuracy: {}".format(res.accuracy))
     log("test loss: {}".format(res.loss))
     log("confusion matrix (rows: label, columns: predicted):")

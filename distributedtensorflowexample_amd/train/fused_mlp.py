@@ -98,6 +98,20 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   exchange engines, the three-launch direct step, the persistent launch, ``DTFX_MLP_KS=14`` and
   the fused flush refuse them.  ``weight_decay=0, nesterov=False`` launches exactly today's
   kernels.
+* ``activation`` (``--activation``; ``ops/hidden_act.py`` has the definition): the hidden
+  activation, ``sigmoid`` (the reference's, the default), ``relu`` or ``tanh``.  The activation
+  and its derivative live in the head launch alone, and every derivative is formed from the h
+  the lane already holds (``h (1 - h)``, ``[h > 0]``, ``1 - h^2``): no load, no launch and no
+  workspace word is added, and every first launch, the flush and the weight-gradient launch
+  are the ones they were (they read the factors).  relu / tanh instantiations exist for the
+  lean head and the three-launch head, plain and with dropout (the derivative then uses the
+  undropped h).  Works with every optimizer, schedule, decay, shuffle and dropout through
+  ``step()``, graph replay, ``run_launched``, ``flush``, ``snapshot``, ``seek`` and the
+  all-reduce engine; ``evaluate`` evaluates with the trainer's activation.  Initialisation is
+  the caller's (the reference's) and a checkpoint does not record the activation.  The
+  exchange engines, the persistent launch, ``DTFX_MLP_KS=14`` and the fused flush have sigmoid
+  heads only and refuse another activation.  ``activation="sigmoid"`` launches exactly today's
+  kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -112,6 +126,7 @@ import time
 import torch
 
 from ..ops import dropout as dropout_mod
+from ..ops import hidden_act
 from ..ops import lr_schedule as lr_schedule_mod
 from ..ops import mlp_step, optim
 from ..ops import weight_decay as weight_decay_mod
@@ -125,7 +140,20 @@ class FusedMLPTrainer:
                  fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
                  beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0,
-                 weight_decay=0.0, adamw=True, nesterov=False):
+                 weight_decay=0.0, adamw=True, nesterov=False, activation="sigmoid"):
+        # --activation: refused first where only the sigmoid head exists
+        self.activation = hidden_act.check(activation)
+        if self.activation != "sigmoid":
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("activation %s: the exchange engines (fused_comm / factor_comm) "
+                                 "have sigmoid heads only; use the all-reduce engine"
+                                 % self.activation)
+            if params.is_cuda and pipeline and allreduce is None and int(world_size) == 1:
+                from ..ops._ext import hip
+
+                if hip().mlp_single_ks() != 28:
+                    raise ValueError("activation %s: DTFX_MLP_KS=14 has no relu / tanh variant; "
+                                     "use the default K slicing" % self.activation)
         # --weight_decay / --nesterov: refused first where the update has no such term
         self.decay = weight_decay_mod.resolve(gpu_ps_optim.check_kind(optimizer), weight_decay,
                                               adamw, nesterov, momentum)
@@ -404,9 +432,10 @@ class FusedMLPTrainer:
         keyword arguments (``predictions``, ``probs``, ``acc``) are the op's.  The parameters
         are ``snapshot()``'s, by its rules: a pending pipelined update on one GPU is flushed,
         the all-reduce engine's pending gradient is applied to a copy, a pending peer exchange
-        raises.  ``global_step()`` is unchanged."""
+        raises.  ``global_step()`` is unchanged.  The hidden activation is the trainer's."""
         from ..ops import mlp_eval
 
+        kw.setdefault("activation", self.activation)
         return mlp_eval.evaluate(self.snapshot(), x, labels, **kw)
 
     def load_params(self, p):
@@ -502,20 +531,22 @@ class FusedMLPTrainer:
                                self.fused_comm)
             return
         if self.direct:
-            mlp_step.step_direct(self.bufs[self.cur], xb, yb, self.ws, self.lr, dropout=self.drop)
+            mlp_step.step_direct(self.bufs[self.cur], xb, yb, self.ws, self.lr, dropout=self.drop,
+                                 activation=self.activation)
             return
         if self.pipelined and self.opt is not None:
             xp = self._xprev(p0)
             mlp_step.step_pipelined_opt(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
                                         self.ws, self.lr, self.pending, self.cur, self.opt,
-                                        dropout=self.drop)
+                                        dropout=self.drop, activation=self.activation)
             self.cur ^= 1
             self.pending = True
             return
         if self.pipelined:
             xp = self._xprev(p0)
             mlp_step.step_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, xb, yb,
-                                    self.ws, self.lr, apply=self.pending, dropout=self.drop)
+                                    self.ws, self.lr, apply=self.pending, dropout=self.drop,
+                                    activation=self.activation)
             self.cur ^= 1
             self.pending = True
             return
@@ -525,14 +556,16 @@ class FusedMLPTrainer:
             # through ops.optim in place, then the step without its deferred apply
             if self.pending:
                 self._apply_reduced(cur, self.opt.slots)
-            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop)
+            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop,
+                               activation=self.activation)
         elif self.pending:
             mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, prev_grad=self.grad,
                                lr=self.lr / self.world_size, p_new=self.bufs[self.cur ^ 1],
-                               dropout=self.drop)
+                               dropout=self.drop, activation=self.activation)
             self.cur ^= 1
         else:
-            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop)
+            mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop,
+                               activation=self.activation)
         if self.allreduce is not None:
             self.allreduce(self.grad)
         self.pending = True
@@ -607,6 +640,9 @@ class FusedMLPTrainer:
         if self.drop is not None and flush and _flush_fused():
             raise ValueError("dropout: the fused flush (DTFX_MLP_FLUSH_FUSED) has no dropout "
                              "variant")
+        if self.activation != "sigmoid" and flush and _flush_fused():
+            raise ValueError("activation %s: the fused flush (DTFX_MLP_FLUSH_FUSED) has a sigmoid "
+                             "head only; flush in its own launch" % self.activation)
         if self.decay is not None and flush and _flush_fused():
             raise ValueError("weight_decay / nesterov: the fused flush (DTFX_MLP_FLUSH_FUSED) has "
                              "no weight-decay variant; flush in its own launch")
@@ -624,8 +660,11 @@ class FusedMLPTrainer:
                                            *oargs)
                 if self.drop is not None:
                     plan.set_drop(*self.drop.args())
+                if self.activation != "sigmoid":
+                    plan.set_act(hidden_act.act_id(self.activation))
                 a = self._host_args = (plan.run, self.device.index, None)
-            elif self.drop is not None or os.environ.get("DTFX_MLP_PLAN", "1") != "0":
+            elif (self.drop is not None or self.activation != "sigmoid"
+                  or os.environ.get("DTFX_MLP_PLAN", "1") != "0"):
                 # the buffers bound once in a C++ plan: the call before the first kernel
                 # converts 7 arguments instead of 17 (a short timed region starts on the host)
                 plan = hip().MlpRunPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
@@ -633,6 +672,8 @@ class FusedMLPTrainer:
                                         ptr(ws.ctr), ptr(ws.stats), ws.stats_ring, self.B)
                 if self.drop is not None:
                     plan.set_drop(*self.drop.args())
+                if self.activation != "sigmoid":
+                    plan.set_act(hidden_act.act_id(self.activation))
                 a = self._host_args = (plan.run, self.device.index, None)
             else:  # (A/B: the 17-argument entry point)
                 a = self._host_args = (hip().mlp_run_pipelined, self.device.index,
@@ -704,7 +745,8 @@ class FusedMLPTrainer:
         """The plain single-GPU step with batch <= 128 can run as ONE persistent launch (not in
         shuffle mode: that launch wraps around one dataset buffer inside the kernel)."""
         return (self.host_loop_ok and self.world_size == 1 and self.B <= 128
-                and not self.shuffle and self.opt is None and self.drop is None)
+                and not self.shuffle and self.opt is None and self.drop is None
+                and self.activation == "sigmoid")
 
     def run_persistent(self, steps, timeout_s=2.0, trace=None):
         """``steps`` complete SGD steps (every update applied, nothing left pending) in ONE
@@ -721,6 +763,9 @@ class FusedMLPTrainer:
                              "(lr_schedule is not supported)")
         if self.drop is not None:
             raise ValueError("run_persistent: the persistent launch has no dropout variant")
+        if self.activation != "sigmoid":
+            raise ValueError("run_persistent: the persistent launch has a sigmoid head only "
+                             "(activation %s is not supported)" % self.activation)
         if self.decay is not None:
             raise ValueError("run_persistent: the persistent launch has no weight-decay or "
                              "Nesterov variant; use run() / run_launched()")

@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from ..models import mlp as mlp_model
 from ..ops import dropout as dropout_mod
+from ..ops import hidden_act
 from ..ops import lr_schedule, mlp_step, nn, optim
 from ..ops import weight_decay as weight_decay_mod
 from ..ops.shuffle import shuffle_index
@@ -87,6 +88,9 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     decay = weight_decay_mod.from_flags(flags)
     if decay is not None and getattr(flags, "zero1", False):
         weight_decay_mod.refuse(flags, "--zero1 (the sharded update)")
+    # --activation: the hidden activation of the fused step's head, the evaluation kernel and the
+    # autograd path (ops/hidden_act.py); a checkpoint does not record it
+    act = hidden_act.from_flags(flags)
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -142,11 +146,12 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         fused = factor = x_all = None
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
-                and opt_kind == "sgd" and sched is None and drop is None and decay is None):
+                and opt_kind == "sgd" and sched is None and drop is None and decay is None
+                and act == "sigmoid"):
             # exchange engine (fused into the backward kernel / factor all-gather) when
             # verified and faster than the all-reduce engine (sgd at a constant rate without
-            # dropout or weight decay only: with an optimizer, a schedule, --dropout or
-            # --weight_decay the all-reduce engine it is)
+            # dropout or weight decay and the sigmoid head only: with an optimizer, a schedule,
+            # --dropout, --weight_decay or --activation relu | tanh the all-reduce engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -171,7 +176,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              lr_schedule=sched, dropout=drop_rate, dropout_seed=drop_seed,
                              weight_decay=decay.wd if decay else 0.0,
                              adamw=decay.adamw if decay else True,
-                             nesterov=decay.nesterov if decay else False, **opt_kw)
+                             nesterov=decay.nesterov if decay else False, activation=act,
+                             **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -181,7 +187,7 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         get_state = lambda: tr.snapshot(with_slots=True)  # noqa: E731
         step_fn = None
     else:
-        model = mlp_model.MnistMLP(flat=params)
+        model = mlp_model.MnistMLP(flat=params, activation=act)
         zero1 = bool(getattr(flags, "zero1", False)) and comm is not None
         ddp = DistributedDataParallel(model, comm, shard=zero1) if comm else None
         zopt = (ShardedOptimizer(GradientDescentOptimizer(flags.learning_rate), ddp)
@@ -306,7 +312,10 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             return float(res.accuracy), float(res.loss)
         p = get_params()
         W1t, b1, W2t, b2 = mlp_step.unflatten(p)
-        h = nn.gemm(test_x, W1t, trans_b=True, bias=b1, act="sigmoid")
+        if act == "tanh":  # (not an epilogue of the generic GEMM)
+            h = torch.tanh(nn.gemm(test_x, W1t, trans_b=True, bias=b1))
+        else:
+            h = nn.gemm(test_x, W1t, trans_b=True, bias=b1, act=act)
         logits = nn.gemm(h, W2t, trans_b=True, bias=b2)
         acc = float((logits.argmax(1).cpu().numpy() == test_y).mean())
         if not eval_summaries:

@@ -44,6 +44,9 @@ def train_model_mirrored(flags, log=print):
     from ..ops import dropout
 
     dropout.refuse(flags, "--model %s" % flags.model)
+    from ..ops import hidden_act
+
+    hidden_act.refuse(flags, "--model %s" % flags.model)
     from ..ops import weight_decay
 
     weight_decay.refuse(flags, "--model %s (it has its own weight decay)" % flags.model)

@@ -149,6 +149,11 @@ class Worker:
         from ..ops import weight_decay
 
         weight_decay.refuse(flags, "--strategy ps_async (--ps_device cpu and gpu)")
+        # --activation: the generic dense layers' epilogues, sigmoid | relu (tanh: mirrored only)
+        from ..ops import hidden_act
+
+        hidden_act.from_flags(flags, allowed=("sigmoid", "relu"),
+                              what="--strategy ps_async (the generic dense layers)")
         if device is None or device == "auto":
             device = "cuda" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)

@@ -47,6 +47,21 @@ def main(argv=None):
 
     _install_signal_handlers()
 
+    # --activation: validated once (ops/hidden_act.py); never silently ignored
+    from distributedtensorflowexample_amd.ops import hidden_act
+
+    try:
+        if FLAGS.job_name == "eval":
+            hidden_act.from_flags(FLAGS)
+        elif FLAGS.strategy != "mirrored":
+            hidden_act.from_flags(FLAGS, allowed=("sigmoid", "relu"),
+                                  what="--strategy ps_async (the generic dense layers)")
+        elif FLAGS.model != "mlp":
+            hidden_act.refuse(FLAGS, "--model %s" % FLAGS.model)
+        else:
+            hidden_act.from_flags(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if FLAGS.job_name == "eval":
         # the latest checkpoint of --logdir on the test set: no server, no process group
         from distributedtensorflowexample_amd.train.eval_job import eval_job
