@@ -315,6 +315,38 @@ PYBIND11_MODULE(_hip, m) {
         P<int>(ctr), P<float>(stats), ring, B, par,
         wd_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb), S(s));
   }, "the flush of mlp_lean_fwdapply_wd");
+  // The same two launches with a moving average of the parameters (ops/ema.py): the weight-decay
+  // form's arguments (without decay: l2, dec, na, nb = 0, 0, 0, 1), then the shadow plane se, omd =
+  // 1 - decay and the num_updates flag.
+  static const auto ema_opt = [](int kind, uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0,
+                                 float h1, float h2, int sched, uintptr_t lrs, float l2, float dec,
+                                 float na, float nb, uintptr_t se, float omd, int nu) {
+    dtfx::MlpOpt o = wd_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb);
+    o.ema = 1, o.se = P<float>(se), o.omd = omd, o.nu = nu ? 1 : 0;
+    return o;
+  };
+  m.def("mlp_lean_fwdapply_ema", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                                    uintptr_t x, uintptr_t ws, uintptr_t ctr, uintptr_t stats,
+                                    int ring, int B, int apply, int par, int kind, uintptr_t s0,
+                                    uintptr_t s1, uintptr_t tp, float h0, float h1, float h2,
+                                    int sched, uintptr_t lrs, float l2, float dec, float na,
+                                    float nb, uintptr_t se, float omd, int nu, uintptr_t s) {
+    dtfx::mlp_lean_fwdapply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<const float>(x),
+        P<float>(ws), P<int>(ctr), P<float>(stats), ring, B, apply, par,
+        ema_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb, se, omd, nu), S(s));
+  }, "mlp_lean_fwdapply_wd that also updates the shadow plane se in place: shadow -= (1 - d_t) * "
+     "(shadow - p_new) by the lane that stores p_new; apply=0 touches no shadow byte");
+  m.def("mlp_apply_ema", [](uintptr_t p_old, uintptr_t p_new, float lr, uintptr_t x_prev,
+                            uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int par,
+                            int kind, uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1,
+                            float h2, int sched, uintptr_t lrs, float l2, float dec, float na,
+                            float nb, uintptr_t se, float omd, int nu, uintptr_t s) {
+    dtfx::mlp_apply_opt_launch(
+        P<const float>(p_old), P<float>(p_new), lr, P<const float>(x_prev), P<float>(ws),
+        P<int>(ctr), P<float>(stats), ring, B, par,
+        ema_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb, se, omd, nu), S(s));
+  }, "the flush of mlp_lean_fwdapply_ema");
   m.def("mlp_lr_sched", [](uintptr_t ctr, uintptr_t blk, float lr0, uintptr_t out, uintptr_t lrs,
                            int ring, uintptr_t s) {
     dtfx::mlp_lr_sched_launch(P<const int>(ctr), P<const int>(blk), lr0, P<float>(out),
@@ -347,6 +379,16 @@ PYBIND11_MODULE(_hip, m) {
         // the weight-decay / Nesterov form (mlp_lean_fwdapply_wd)
         return MlpRunOptPlan{bound(p0, p1, x, lab, nbatches, ws, ctr, stats, ring, B),
                              wd_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb)};
+      }))
+      .def(py::init([](uintptr_t p0, uintptr_t p1, uintptr_t x, uintptr_t lab, int nbatches,
+                       uintptr_t ws, uintptr_t ctr, uintptr_t stats, int ring, int B, int kind,
+                       uintptr_t s0, uintptr_t s1, uintptr_t tp, float h0, float h1, float h2,
+                       int sched, uintptr_t lrs, float l2, float dec, float na, float nb,
+                       uintptr_t se, float omd, int nu) {
+        // the moving-average form (mlp_lean_fwdapply_ema)
+        return MlpRunOptPlan{bound(p0, p1, x, lab, nbatches, ws, ctr, stats, ring, B),
+                             ema_opt(kind, s0, s1, tp, h0, h1, h2, sched, lrs, l2, dec, na, nb, se,
+                                     omd, nu)};
       }))
       .def("run", [](const MlpRunOptPlan& p, int cur, int pending, float lr, int pos, int n,
                      int flush, uintptr_t s) {
@@ -411,6 +453,12 @@ PYBIND11_MODULE(_hip, m) {
                       P<const float>(lr_ptr), b1, b2, eps, wd, adamw, step, P<const int>(step_ptr),
                       S(s));
   });
+  m.def("ema", [](long long n, uintptr_t shadow, uintptr_t p, float omd, bool num_updates, int step,
+                  uintptr_t step_ptr, uintptr_t s) {
+    dtfx::ema_launch(n, P<float>(shadow), P<const float>(p), omd, num_updates, step,
+                     P<const int>(step_ptr), S(s));
+  }, "shadow -= (1 - d_t) * (shadow - p) in place (omd = 1 - decay; num_updates: d_t = "
+     "min(decay, (1 + t) / (10 + t)), t = *step_ptr or step)");
   m.def("scale", [](long long n, uintptr_t x, float a, uintptr_t s) {
     dtfx::scale_launch(n, P<float>(x), a, S(s));
   });

@@ -33,6 +33,8 @@ void momentum_launch(long long n, float* p, const float* g, float* v, float lr, 
 void adam_launch(long long n, float* p, const float* g, float* m, float* v, float lr,
                  const float* lr_ptr, float b1, float b2, float eps, float wd, bool adamw, int step,
                  const int* step_ptr, hipStream_t s);
+void ema_launch(long long n, float* shadow, const float* p, float omd, bool num_updates, int step,
+                const int* step_ptr, hipStream_t s);
 void scale_launch(long long n, float* x, float a, hipStream_t s);
 void counter_add_launch(int* c, int d, hipStream_t s);
 void philox_init_launch(long long n, float* out, unsigned long long seed, unsigned long long offset,

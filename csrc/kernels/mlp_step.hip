@@ -612,9 +612,27 @@ void mlp_head2_single_launch(const float* p, const int* labels, float* ws, int B
 // wd != 0: the weight-decay / Nesterov instantiations (mlp_lean_fwdapply_wd_kernel) with the
 // coefficients l2, dec, na, nb (ops/weight_decay.py: words()); kind 0 is then allowed at a
 // constant rate too (tp: the plain step pair, no slot plane).
+// ema != 0: the moving-average instantiations (mlp_lean_fwdapply_ema_kernel) with the shadow plane
+// se, omd = 1 - decay and the num_updates flag (ops/ema.py: words()); every kind 0..2, with or
+// without a schedule and the weight-decay words.
 static void check_opt(const MlpOpt& o, const char* who) {
   const char* bad = nullptr;  // (the message is put together only when there is one)
-  if (o.wd && !o.sched) {
+  if (o.ema) {
+    if (o.kind != mlp::OPT_SGD && o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
+      bad = ": moving-average optimizer kind must be 0 (sgd), 1 or 2";
+    else if (mlp_single_ks() != mlp::KS3)
+      bad = ": DTFX_MLP_KS=14 has no moving-average variant";
+    else if (!o.tp || (o.kind != mlp::OPT_SGD && !o.s0) || (o.kind == mlp::OPT_ADAM && !o.s1))
+      bad = ": null slot plane / step pair";
+    else if (o.sched && (reinterpret_cast<uintptr_t>(o.tp) & 31))
+      bad = ": the schedule block must be 32-byte aligned";
+    else if (!o.se)
+      bad = ": null shadow plane";
+    else if (reinterpret_cast<uintptr_t>(o.se) & 15)
+      bad = ": the shadow plane must be 16-byte aligned";
+    else if (!(o.omd > 0.f && o.omd < 1.f))
+      bad = ": the moving-average decay must lie in (0, 1)";
+  } else if (o.wd && !o.sched) {
     if (o.kind != mlp::OPT_SGD && o.kind != mlp::OPT_MOMENTUM && o.kind != mlp::OPT_ADAM)
       bad = ": weight-decay optimizer kind must be 0 (sgd), 1 or 2";
     else if (mlp_single_ks() != mlp::KS3)
@@ -659,7 +677,16 @@ static void lean_first_opt_launch(const float* p_old, float* p_new, float lr, co
   // (check_opt has admitted the kind: 0..2 scheduled, 1..2 not)
   const char* bad_kind = "fused MLP step: optimizer kind out of range";
   with_ngt(B, [&](auto NGT) {
-    if (o.wd)
+    if (o.ema)  // (without decay the coefficient words are MlpOpt's defaults 0, 0, 0, 1)
+      with_const<OPT_SGD, OPT_MOMENTUM, OPT_ADAM>(o.kind, bad_kind, [&](auto OPTK) {
+        with_flag(o.sched != 0, [&](auto SCHED) {
+          hipLaunchKernelGGL((mlp_lean_fwdapply_ema_kernel<NGT(), FWD, OPTK(), SCHED()>), grid,
+                             block, 0, stream, p_old, p_new, x_prev, x, ws, lr, flags, ctr, stats,
+                             o.s0, o.s1, o.tp, o.h0, o.h1, o.h2, oflags | (o.nu ? 4 : 0),
+                             SCHED() ? o.lrs : nullptr, o.l2, o.dec, o.na, o.nb, o.se, o.omd);
+        });
+      });
+    else if (o.wd)
       with_const<OPT_SGD, OPT_MOMENTUM, OPT_ADAM>(o.kind, bad_kind, [&](auto OPTK) {
         with_flag(o.sched != 0, [&](auto SCHED) {
           hipLaunchKernelGGL((mlp_lean_fwdapply_wd_kernel<NGT(), FWD, OPTK(), SCHED()>), grid,
@@ -855,7 +882,8 @@ void mlp_run_pipelined_opt_launch(float* p0, float* p1, int cur, int pending, fl
   if (flush && mlp_flush_fused())
     throw std::runtime_error(
         std::string("mlp_run_pipelined_opt: the fused flush (DTFX_MLP_FLUSH_FUSED) has ") +
-        (o.wd      ? "no weight-decay variant"
+        (o.ema     ? "no moving-average variant"
+         : o.wd    ? "no weight-decay variant"
          : o.sched ? "no learning-rate schedule variant"
                    : "no optimizer variant (sgd only)"));
   auto step = [&](const float* po, float* pn, const float* xprev, const float* xcur,

@@ -418,16 +418,19 @@ __global__ __launch_bounds__(64) void mlp_head_drop_kernel(
 // rewrites its slot values (addresses clamped like p_src's, stores behind the p store's
 // predicate and oa.apply); the stats lane hands the step word on (tp[par ^ 1]).
 // WD: the weight-decay / Nesterov family (opt_update<OPT, WD>); decay reaches b1 / W2 / b2 here.
+// EMA: the owning lane also reads and rewrites its shadow value (ema_update of the new parameter
+// value, behind the p store's predicate and oa.apply), so the shadow covers b1 / W2 / b2.
 template <bool DIRECT, int NGT, int XW, bool RM = false, int OPT = OPT_SGD, bool SCHED = false,
-          bool WD = false>
+          bool WD = false, bool EMA = false>
 __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx,
                                             float* __restrict__ p, float lr,
                                             float* __restrict__ grad, const Bufs& w,
                                             int* __restrict__ ctr, float* __restrict__ stats,
                                             int stats_ring, int B, const MlpXg& xg,
                                             const float* __restrict__ p_src = nullptr,
-                                            int stats_on = 1, const OptArgs& oa = OptArgs{}) {
-  constexpr bool OX = OPT != OPT_SGD || SCHED || WD;  // the OptArgs path (sgd: no slots)
+                                            int stats_on = 1,
+                                            const OptArgsOf<EMA>& oa = OptArgsOf<EMA>{}) {
+  constexpr bool OX = OPT != OPT_SGD || SCHED || WD || EMA;  // the OptArgs path (sgd: no slots)
   static_assert(!OX || (DIRECT && XW == 0), "optimizer variants: the lean step only");
   if (p_src == nullptr) p_src = p;
   const int BP = NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16;
@@ -516,6 +519,7 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
   bool ok[4];
   float pv[4];
   float sa[4] = {0.f, 0.f, 0.f, 0.f}, sb[4] = {0.f, 0.f, 0.f, 0.f};  // OPT: slot values
+  [[maybe_unused]] EmaRegs<EMA> em;  // EMA: shadow values and 1 - d_t (else: nothing at all)
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     if (dw2) {  // C[c = q*4+i][j = jt*16 + r] -> dW2t[c][j]; SPLIT: wave 0 i < 2, wave 2 i >= 2
@@ -534,11 +538,13 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
     if (DIRECT) pv[i] = p_src[off[i]];
     if constexpr (OPT != OPT_SGD) sa[i] = oa.s0[off[i]];
     if constexpr (OPT == OPT_ADAM) sb[i] = oa.s1[off[i]];
+    if constexpr (EMA) em.e[i] = oa.se[off[i]];
   }
   (void)db2;
   __builtin_amdgcn_sched_barrier(0);
   [[maybe_unused]] OptCoef oc = {};  // (adam's b1^t / b2^t while the loads are in flight)
   if constexpr (OX) oc = opt_coef<OPT, SCHED, WD>(lr, oa);
+  if constexpr (EMA) em.om = ema_omd(oa);  // (1 - d_t of the step applied, once per wave)
   // NB: padded batch columns of dz1T/dlT are zero, so multiplying by 1 is exact.
   f32x4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
 #pragma unroll
@@ -604,6 +610,9 @@ __device__ __forceinline__ void wgrad_small(int jt, int wave, int lane, int eidx
             oa.s0[off[i]] = sa[i];
             if constexpr (OPT == OPT_ADAM) oa.s1[off[i]] = sb[i];
           }
+        }
+        if constexpr (EMA) {
+          if (oa.apply) oa.se[off[i]] = ema_update(em.e[i], pn, em.om);
         }
       }
     }

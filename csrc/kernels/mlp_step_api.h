@@ -92,6 +92,15 @@ struct MlpOpt {
   // gradient descent with the step pair and no slot plane, scheduled or not.
   int wd = 0;
   float l2 = 0.f, dec = 0.f, na = 0.f, nb = 1.f;
+  // ema != 0: the moving-average instantiations (ops/ema.py: words()).  se: the shadow plane (flat
+  // f32 [79510], 16-byte aligned), updated in place by shadow -= (1 - d_t) * (shadow - p_new);
+  // omd = 1 - decay, 0 < omd < 1; nu != 0: d_t = min(decay, (1 + t) / (10 + t)).  Every kind
+  // 0..2, scheduled or not, with or without the weight-decay words (kind 0: the step pair and no
+  // slot plane).
+  int ema = 0;
+  float* se = nullptr;
+  float omd = 0.f;
+  int nu = 0;
 };
 void mlp_lean_fwdapply_opt_launch(const float* p_old, float* p_new, float lr, const float* x_prev,
                                   const float* x, float* ws, int* ctr, float* stats,

@@ -91,18 +91,22 @@ namespace mlp {
 // would let the compiler sink them below the barrier).
 // WD (weight decay / Nesterov; see OptArgs): the same item with opt_update<OPT, WD> -- pw4 is the
 // decayed value, so no load is added; apply == 0 stays the copy.
+// EMA (the moving average of the parameters; see EmaOptArgs): the item's shadow float4 is requested
+// at the slot position, after pw4 and the slots at the same clamped address; once v is selected
+// the item stores ema_update(shadow, v) under the p_new store's predicate and oa.apply.
 template <int NGT, int XW = 0, bool TRACE = false, bool TWO = false, int KSX = KS2, bool FWD = true,
           bool ORD = false, bool A16 = false, int OPT = OPT_SGD, bool SCHED = false,
-          bool WD = false>
+          bool WD = false, bool EMA = false>
 __device__ __forceinline__ void fwdapply_block(
     const int bid, const float* __restrict__ p_old, float* __restrict__ p_new, float lr,
     const float* __restrict__ x_prev, const float* __restrict__ x, const Bufs& w,
     int* __restrict__ ctr, float* __restrict__ stats, int stats_ring, int B, int stats_on,
     const MlpXg& xg, unsigned long long* __restrict__ tr,
-    unsigned long long* __restrict__ trs = nullptr, const OptArgs& oa = OptArgs{}) {
+    unsigned long long* __restrict__ trs = nullptr,
+    const OptArgsOf<EMA>& oa = OptArgsOf<EMA>{}) {
   static_assert(!ORD || (XW == 0 && KSX == KS3), "load order of the row-quad form");
   static_assert(!A16 || ORD, "the 16-byte apply belongs to the lean step");
-  constexpr bool OX = OPT != OPT_SGD || SCHED || WD;  // the OptArgs path (sgd: no slots)
+  constexpr bool OX = OPT != OPT_SGD || SCHED || WD || EMA;  // the OptArgs path (sgd: no slots)
   static_assert(!OX || (A16 && !TRACE), "optimizer variants: the lean step only");
   // stamps per wave: 0 entry, 1 phase-A operands landed, 2 W1 tile applied + barrier, 3 slab
   // stored; with XW > 0 also 4 local gradient slice ready (exchange starts), 5 two-shot: the
@@ -126,8 +130,9 @@ __device__ __forceinline__ void fwdapply_block(
   if (bid >= HT * KSX) {
     const int jt = bid - HT * KSX;
     if constexpr (OX)
-      wgrad_small<true, NGT, XW, RM, OPT, SCHED, WD>(jt, wave, lane, 0, p_new, lr, nullptr, w, ctr,
-                                                     stats, stats_ring, B, xg, p_old, stats_on, oa);
+      wgrad_small<true, NGT, XW, RM, OPT, SCHED, WD, EMA>(jt, wave, lane, 0, p_new, lr, nullptr, w,
+                                                          ctr, stats, stats_ring, B, xg, p_old,
+                                                          stats_on, oa);
     else
     wgrad_small<true, NGT, XW, RM>(jt, wave, lane, MLP_XG_SMALL_EPOCH + jt * 4 + wave, p_new, lr,
                                nullptr, w, ctr, stats, stats_ring, B, xg, p_old, stats_on);
@@ -184,6 +189,7 @@ __device__ __forceinline__ void fwdapply_block(
     const int hw = item / MQ, mw = item % MQ, jw = jt * 16 + hw;
     float4 pw4 = {0.f, 0.f, 0.f, 0.f};
     float4 sa4 = {0.f, 0.f, 0.f, 0.f}, sb4 = {0.f, 0.f, 0.f, 0.f};  // OPT: the item's slot values
+    [[maybe_unused]] EmaRegs<EMA, float4> em;  // EMA: its shadow values and 1 - d_t
     auto load_pw = [&]() {
       if constexpr (A16) {
         pw4 = f4(p_old + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
@@ -191,6 +197,8 @@ __device__ __forceinline__ void fwdapply_block(
           sa4 = f4(oa.s0 + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
         if constexpr (OPT == OPT_ADAM)
           sb4 = f4(oa.s1 + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
+        if constexpr (EMA)
+          em.e = f4(oa.se + OFF_W1 + (size_t)(jw < H ? jw : H - 1) * D + f0 + 4 * mw);
       } else if (wave < 2) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -222,6 +230,7 @@ __device__ __forceinline__ void fwdapply_block(
     // (OPT: adam's b1^t / b2^t while the loads are in flight, not between the sum and the store)
     [[maybe_unused]] OptCoef oc = {};
     if constexpr (OX) oc = opt_coef<OPT, SCHED, WD>(lr, oa);
+    if constexpr (EMA) em.om = ema_omd(oa);  // (1 - d_t of the step applied, once per wave)
     if constexpr (TRACE && NGT > 0 && FWD) {
       if (trs) {  // loads issued after the first class: ORD pw + xa, else pw + the factors
         unsigned long long* t2 = trs + (size_t)(bid * 4 + wave) * 2;
@@ -267,6 +276,13 @@ __device__ __forceinline__ void fwdapply_block(
             *reinterpret_cast<float4*>(so) = sa4;
             if constexpr (OPT == OPT_ADAM)
               *reinterpret_cast<float4*>(oa.s1 + (so - oa.s0)) = sb4;
+          }
+        }
+        if constexpr (EMA) {  // (after the select: v is the value the p_new store writes)
+          if (oa.apply && lane < IPW && live) {
+            const float4 e = {ema_update(em.e.x, v.x, em.om), ema_update(em.e.y, v.y, em.om),
+                              ema_update(em.e.z, v.z, em.om), ema_update(em.e.w, v.w, em.om)};
+            *reinterpret_cast<float4*>(oa.se + OFF_W1 + (size_t)jw * D + f0 + 4 * mw) = e;
           }
         }
       } else {
@@ -521,15 +537,20 @@ __global__ __launch_bounds__(256) void mlp_fwdapply_kernel(
 // The data-parallel engines, mlp_fwdapply_launch / mlp_head2_launch and the opt-in fused flush
 // keep mlp_fwdapply_kernel / mlp_head_kernel.
 
-template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD, bool SCHED = false, bool WD = false>
+template <int NGT, bool TRACE, bool FWD, int OPT = OPT_SGD, bool SCHED = false, bool WD = false,
+          bool EMA = false>
 __device__ __forceinline__ void lean_fwdapply_body(
     const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
     const float* __restrict__ x, float* __restrict__ ws, int* __restrict__ ctr,
     float* __restrict__ stats, float lr, int flags, unsigned long long* __restrict__ tr,
-    unsigned long long* __restrict__ trs, const OptArgs& oa = OptArgs{}) {
+    unsigned long long* __restrict__ trs, const OptArgsOf<EMA>& oa = OptArgsOf<EMA>{}) {
   const int B = flags & 511, stats_on = (flags >> 9) & 1, stats_ring = flags >> 10;
   const Bufs w = ws_bufs(ws, NGT > 0 ? NGT * 16 : ((B + 15) >> 4) * 16);
-  if constexpr (WD)
+  if constexpr (EMA)
+    fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT, SCHED, WD, true>(
+        blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{},
+        tr, trs, oa);
+  else if constexpr (WD)
     fwdapply_block<NGT, 0, TRACE, false, KS3, FWD, true, true, OPT, SCHED, true>(
         blockIdx.x, p_old, p_new, lr, x_prev, x, w, ctr, stats, stats_ring, B, stats_on, MlpXg{},
         tr, trs, oa);
@@ -596,6 +617,28 @@ __global__ __launch_bounds__(256) void mlp_lean_fwdapply_wd_kernel(
   const OptArgs oa = {s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1, lrs, l2, dec, na, nb};
   lean_fwdapply_body<NGT, false, FWD, OPT, SCHED, true>(p_old, p_new, x_prev, x, ws, ctr, stats,
                                                         lr, flags, nullptr, nullptr, oa);
+}
+
+// The moving-average instantiations (EmaOptArgs): the weight-decay kernel's arguments,
+// then the shadow plane and 1 - decay; oflags bit 2 is the num_updates flag.  ONE family for every
+// optimizer with and without decay: the block is always the WD one, and without decay the
+// coefficients are OptArgs' defaults (l2, dec, na, nb) = (0, 0, 0, 1), with which every WD term is
+// exact for finite values -- fma(0, p, g) = g, 0 * g' + 1 * accum = accum, p - 0 * p = p -- so
+// the parameters and slots are the non-WD kernels' bits (tests/test_fused_ema_gpu.py).  OPT_SGD
+// is gradient descent with the step pair and no slot plane, as in the WD family.
+template <int NGT, bool FWD, int OPT, bool SCHED>
+__global__ __launch_bounds__(256) void mlp_lean_fwdapply_ema_kernel(
+    const float* __restrict__ p_old, float* __restrict__ p_new, const float* __restrict__ x_prev,
+    const float* __restrict__ x, float* __restrict__ ws, float lr, int flags,
+    int* __restrict__ ctr, float* __restrict__ stats, float* __restrict__ s0,
+    float* __restrict__ s1, int* __restrict__ tp, float h0, float h1, float h2, int oflags,
+    float* __restrict__ lrs, float l2, float dec, float na, float nb, float* __restrict__ se,
+    float omd) {
+  const EmaOptArgs oa = {{s0, s1, tp, h0, h1, h2, oflags & 1, (oflags >> 1) & 1, lrs, l2, dec, na,
+                          nb}, se, omd, (oflags >> 2) & 1};
+  lean_fwdapply_body<NGT, false, FWD, OPT, SCHED, true, true>(p_old, p_new, x_prev, x, ws, ctr,
+                                                              stats, lr, flags, nullptr, nullptr,
+                                                              oa);
 }
 
 template <int NGT>

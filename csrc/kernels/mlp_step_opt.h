@@ -8,6 +8,9 @@
 // of that entry point -- sgd among them -- compute the rate of the step they apply from the step
 // word and an 8-word schedule block, once per wave, and the stats lane publishes it to a rate
 // ring; the constant-rate kernels are unchanged (profiles/lr_schedule/: +0.03 .. +0.2 us a step).
+// Moving average of the parameters (ema_omd / ema_update, mlp_lean_fwdapply_ema_kernel): the lane
+// that stores a new parameter value also reads and rewrites its element of a shadow plane, as it
+// does its slot values; every other kernel is unchanged (profiles/ema/).
 #pragma once
 #include "mlp_step_ws.h"
 
@@ -41,6 +44,21 @@ struct OptArgs {
   // WD (mlp_lean_fwdapply_wd_kernel): wave-uniform coefficients, read by that family alone
   float l2 = 0.f, dec = 0.f, na = 0.f, nb = 1.f;
 };
+// EMA (mlp_lean_fwdapply_ema_kernel): OptArgs, then the shadow plane, 1 - decay and the
+// num_updates flag.  A type of its own, which only the EMA instantiations name (OptArgsOf): three
+// more members in OptArgs itself grew the defaulted temporary at every other call site, and
+// three traced exchange kernels came out with one renamed register (profiles/ema/).
+struct EmaOptArgs : OptArgs {
+  float* se = nullptr;
+  float omd = 0.f;
+  int nu = 0;
+};
+template <bool EMA>
+struct OptArgsSel { typedef OptArgs type; };
+template <>
+struct OptArgsSel<true> { typedef EmaOptArgs type; };
+template <bool EMA>
+using OptArgsOf = typename OptArgsSel<EMA>::type;
 // Weight decay and Nesterov momentum (the WD instantiations; ops/weight_decay.py is the
 // definition, which is ops/optim.py's and torch.optim's).  g' = g + l2 * p is the gradient
 // every kind uses -- the parameter is already in the owning lane's registers -- and
@@ -51,6 +69,15 @@ struct OptArgs {
 //             adamw: l2 = 0, dec = wd (decoupled);  not adamw: l2 = wd, dec = 0
 // rate is the rate of the step applied: sched_rate's value with a schedule, never adam's
 // bias-corrected c.lr.  Decay is uniform over the flat buffer, biases included.
+// Moving average of the parameters (the EMA instantiations; ops/ema.py is the definition, which
+// is tf.train.ExponentialMovingAverage's): se is one more flat f32 [NPARAM] plane in the
+// parameter layout, read and rewritten IN PLACE by the lane that owns the element, after the
+// update of step s (t = s + 1) has produced the new value v, in TF's assign_sub form
+//   shadow -= (1 - d_t) * (shadow - v)
+//   d_t = decay, or with num_updates min(decay, (1 + t) / (10 + t)): 1 - d_t = max(omd, 9 / (10 + t))
+// 1 - d_t is wave-uniform (ema_omd: once per wave from the step word tp[par], a correctly rounded
+// division; ops/ema.py's one_minus_decay_f32 is this arithmetic operation for operation).  The
+// shadow never feeds back into the update, and apply == 0 writes no shadow byte.
 // Learning-rate schedules evaluated on the device (the SCHED instantiations; ops/lr_schedule.py
 // is the definition, its value_f32 this arithmetic operation for operation).  The step pair is
 // then the head of an 8-word block [tp0, tp1, kind | staircase << 2, decay_steps, a, inv_decay,
@@ -139,6 +166,27 @@ __device__ __forceinline__ float opt_update(float p, float g, float& s0, float& 
     return p - c.lr * s0 * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(s1) * c.rbc2 + c.h2);
   }
 }
+
+// EMA: 1 - d_t of the step applied, and the new shadow value of one element.  The branch on the
+// num_updates flag is wave-uniform (a kernel argument): without it no step word is read and the
+// division's div_scale / fma / fixup sequence does not run.
+__device__ __forceinline__ float ema_omd(const EmaOptArgs& oa) {
+  if (!oa.nu) return oa.omd;
+  const float t = (float)(oa.tp[oa.par] + 1);
+  return fmaxf(oa.omd, 9.f / (10.f + t));
+}
+__device__ __forceinline__ float ema_update(float e, float v, float om) {
+  return e - om * (e - v);
+}
+// the owning lane's shadow values (float4: the W1 item; float[4]: the small parameters) and the
+// wave's 1 - d_t -- an empty type without EMA, so the other instantiations declare nothing
+template <bool EMA, class V = float[4]>
+struct EmaRegs {};
+template <class V>
+struct EmaRegs<true, V> {
+  V e;
+  float om;
+};
 
 // The all-reduce engine's rate (FusedMLPTrainer._apply_reduced): one wave writes lr(s) of the
 // pending step -- s = ctr - 1: the step that produced the gradient has advanced the counter --

@@ -6,6 +6,8 @@
 //   momentum : v = mu * v + g' ; p -= lr * (nesterov ? g' + mu * v : v)
 //   adam(w)  : bias-corrected Adam; decoupled weight decay when adamw
 //   scale    : x *= alpha                        (gradient averaging)
+//   ema      : shadow -= (1 - d_t) * (shadow - p) (tf.train.ExponentialMovingAverage;
+//                                                 ops/ema.py is the definition)
 //
 // All loops are grid-stride over float4 (dwordx4) with a scalar tail.
 // `lr_ptr` / `step_ptr` (optional) let a captured hipGraph pick up a device-side
@@ -108,6 +110,34 @@ __global__ __launch_bounds__(256) void scale_kernel(long long n, float* __restri
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) x[i] *= a;
 }
 
+// shadow -= (1 - d_t) * (shadow - p), in place on the shadow.  omd = 1 - decay; nu: d_t =
+// min(decay, (1 + t) / (10 + t)), i.e. 1 - d_t = max(omd, 9 / (10 + t)) -- the fused step's
+// arithmetic (mlp_step_opt.h: ema_omd), t = *step_ptr (a device counter, so a captured graph picks
+// up the step) or `step`.  vec == 0 (a buffer that is not 16-byte aligned): the scalar loop alone.
+__global__ __launch_bounds__(256) void ema_kernel(long long n, float* __restrict__ e,
+                                                  const float* __restrict__ p, float omd, int nu,
+                                                  int step, const int* __restrict__ step_ptr,
+                                                  int vec) {
+  float om = omd;
+  if (nu) {  // (uniform: a kernel argument)
+    const float t = (float)(step_ptr ? *step_ptr : step);
+    om = fmaxf(omd, 9.f / (10.f + t));
+  }
+  const long long n4 = vec ? n >> 2 : 0;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = i0; i < n4; i += stride) {
+    float4 ev = reinterpret_cast<float4*>(e)[i];
+    const float4 pv = reinterpret_cast<const float4*>(p)[i];
+    ev.x -= om * (ev.x - pv.x);
+    ev.y -= om * (ev.y - pv.y);
+    ev.z -= om * (ev.z - pv.z);
+    ev.w -= om * (ev.w - pv.w);
+    reinterpret_cast<float4*>(e)[i] = ev;
+  }
+  for (long long i = (n4 << 2) + i0; i < n; i += stride) e[i] -= om * (e[i] - p[i]);
+}
+
 __global__ void counter_add_kernel(int* c, int d) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c += d;
 }
@@ -144,6 +174,18 @@ void adam_launch(long long n, float* p, const float* g, float* m, float* v, floa
   check_align(v, "adam");
   hipLaunchKernelGGL(adam_kernel, stream_grid(n >> 2), dim3(256), 0, s, n, p, g, m, v, lr, lr_ptr,
                      b1, b2, eps, wd, adamw ? 1 : 0, step, step_ptr);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+void ema_launch(long long n, float* shadow, const float* p, float omd, bool num_updates, int step,
+                const int* step_ptr, hipStream_t s) {
+  if (n <= 0) return;
+  if (!shadow || !p) throw std::runtime_error("ema: null buffer");
+  if (!(omd > 0.f && omd < 1.f)) throw std::runtime_error("ema: decay must lie in (0, 1)");
+  const bool vec =
+      ((reinterpret_cast<uintptr_t>(shadow) | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+  hipLaunchKernelGGL(ema_kernel, stream_grid(vec ? n >> 2 : n), dim3(256), 0, s, n, shadow, p, omd,
+                     num_updates ? 1 : 0, step, step_ptr, vec ? 1 : 0);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

@@ -253,6 +253,22 @@ def define_reference_flags(flag_values=FLAGS):
                    "--optimizer momentum: Nesterov momentum (tf.train.MomentumOptimizer's "
                    "use_nesterov; p -= lr_t * (g' + mu * accum)); refused with any other "
                    "--optimizer", fv)
+    DEFINE_float("ema_decay", 0.0,
+                 "moving average of the parameters (tf.train.ExponentialMovingAverage, "
+                 "ops/ema.py): decay in (0, 1); 0 = off.  After every update shadow -= (1 - "
+                 "decay) * (shadow - variable), the shadows starting at the initial values.  "
+                 "--strategy mirrored, --model mlp only: inside the fused step's first launch "
+                 "(one GPU), in the all-reduce engine (several) or on the autograd path (--device "
+                 "cpu); checkpoints carry the shadows as <variable>/ExponentialMovingAverage.  "
+                 "ps_async, --model bert|resnet50 and --zero1 refuse it", fv)
+    DEFINE_boolean("ema_num_updates", False,
+                   "--ema_decay: TF's num_updates = global_step, decay_t = min(decay, (1 + t) / "
+                   "(10 + t)) with t the step count after the update (a faster average early "
+                   "on)", fv)
+    DEFINE_boolean("eval_ema", False,
+                   "evaluate the averaged variables instead of the raw ones: the periodic test "
+                   "evaluation of a --ema_decay run, and --job_name eval (which fails if the "
+                   "checkpoint has none)", fv)
     DEFINE_string("cpu_affinity", "numa",
                   "async PS: numa = the ps tasks on GPU 0's NUMA node (--numa_node overrides), "
                   "8 cores each; worker i on 2 cores of its OWN GPU's node, after the ps tasks' "

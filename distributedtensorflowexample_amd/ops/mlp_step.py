@@ -223,20 +223,31 @@ class PipelinedOpt:
 
     ``decay`` (an ``ops.weight_decay.WeightDecay``): the weight-decay / Nesterov instantiations
     (``mlp_lean_fwdapply_wd``), scheduled or not; ``wd_args()`` appends the schedule flag, the
-    rate ring and the four coefficient words.  Kind ``"sgd"`` is allowed then too."""
+    rate ring and the four coefficient words.  Kind ``"sgd"`` is allowed then too.
+
+    ``ema`` (an ``ops.ema.EMA``): the moving-average instantiations (``mlp_lean_fwdapply_ema``)
+    for every kind, ``"sgd"`` included, scheduled or not, with or without ``decay``.  ``shadow``
+    is the shadow plane, one more flat f32 [79510] plane updated in place by the owning lane
+    (zero here: the owner initialises it from its parameters); ``ema_args()`` is ``wd_args()``
+    -- without decay the coefficient words (0, 0, 0, 1) -- then the plane, ``1 - decay`` and the
+    ``num_updates`` flag."""
 
     KINDS = {"momentum": 1, "adam": 2}
 
     def __init__(self, kind, device, momentum=0.9, beta1=0.9, beta2=0.999, epsilon=1e-8,
-                 schedule=None, stats_ring=4096, decay=None):
+                 schedule=None, stats_ring=4096, decay=None, ema=None):
         from ..parallel import gpu_ps_optim
 
         if decay is not None and decay.kind != kind:
             raise ValueError("the weight-decay terms are %s's, the optimizer is %s"
                              % (decay.kind, kind))
         self.decay = decay
+        self.ema = ema
+        self.shadow = (torch.zeros(NPARAM, device=device, dtype=torch.float32)
+                       if ema is not None else None)
         if kind not in self.KINDS and not (
-                kind == "sgd" and (schedule is not None or decay is not None)):
+                kind == "sgd" and (schedule is not None or decay is not None
+                                   or ema is not None)):
             raise ValueError("the fused step's optimizers are momentum and adam, got %r" % (kind,))
         self.kind = kind
         self.code = self.KINDS.get(kind, 0)
@@ -254,6 +265,7 @@ class PipelinedOpt:
             self.tp = self.block[:2]
             self.rates = torch.zeros(int(stats_ring), device=device, dtype=torch.float32)
         _check_flat(*self.slots)
+        _check_flat(self.shadow)
 
     def set_step(self, s):
         """Both words: the next launch reads the right one whatever its parity."""
@@ -276,6 +288,15 @@ class PipelinedOpt:
         return (self.args() + (1 if sched else 0, ptr(self.rates) if (sched and stats) else 0)
                 + self.decay.words())
 
+    def ema_args(self, stats=True):
+        """``wd_args()`` (without decay: the coefficient words that leave the update alone),
+        the shadow plane, ``1 - decay`` and the ``num_updates`` flag, as the moving-average
+        launchers take them."""
+        sched = self.schedule is not None
+        words = self.decay.words() if self.decay is not None else (0.0, 0.0, 0.0, 1.0)
+        return (self.args() + (1 if sched else 0, ptr(self.rates) if (sched and stats) else 0)
+                + words + (ptr(self.shadow),) + self.ema.words())
+
 
 def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, apply, par,
                        opt: PipelinedOpt, stats=True, dropout=None, activation="sigmoid"):
@@ -291,7 +312,14 @@ def step_pipelined_opt(p_old, p_new, x_prev, x, labels, ws: StepWorkspace, lr, a
     if p_old.data_ptr() == p_new.data_ptr():
         raise ValueError("the pipelined step needs distinct ping-pong buffers")
     h, s = hip(), stream_handle()
-    if opt.decay is not None:  # (lr: the base rate with a schedule, else the rate)
+    if opt.ema is not None:  # (lr: the base rate with a schedule, else the rate)
+        if opt.schedule is not None:
+            _check_sched(opt, ws)
+        h.mlp_lean_fwdapply_ema(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
+                                ptr(x), ptr(ws.buf), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
+                                ws.stats_ring, ws.B, 1 if apply else 0, int(par),
+                                *opt.ema_args(stats), s)
+    elif opt.decay is not None:  # (lr: the base rate with a schedule, else the rate)
         if opt.schedule is not None:
             _check_sched(opt, ws)
         h.mlp_lean_fwdapply_wd(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev if apply else x),
@@ -316,6 +344,13 @@ def flush_pipelined_opt(p_old, p_new, x_prev, ws: StepWorkspace, lr, par, opt: P
     """``flush_pipelined`` with momentum / Adam (the apply-only instantiation)."""
     _check(x_prev, None, ws.B)
     _check_flat(p_old, p_new)
+    if opt.ema is not None:
+        if opt.schedule is not None:
+            _check_sched(opt, ws)
+        hip().mlp_apply_ema(ptr(p_old), ptr(p_new), float(lr), ptr(x_prev), ptr(ws.buf),
+                            ptr(ws.ctr), ptr(ws.stats) if stats else 0, ws.stats_ring, ws.B,
+                            int(par), *opt.ema_args(stats), stream_handle())
+        return
     if opt.decay is not None:
         if opt.schedule is not None:
             _check_sched(opt, ws)

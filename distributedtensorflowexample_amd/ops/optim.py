@@ -64,6 +64,32 @@ def adam_(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0
     return p
 
 
+def ema_(shadow, p, decay, num_updates=False, step=0, step_tensor=None):
+    """Moving average of the parameters (``ops/ema.py``), in place on ``shadow``:
+    ``shadow -= (1 - d_t) * (shadow - p)`` with ``d_t = decay`` or, with ``num_updates``,
+    ``min(decay, (1 + t) / (10 + t))``.  ``t`` is 1-based (after increment): ``step``, or the
+    int32 device counter ``step_tensor`` (graph-capturable, as ``adam_`` reads it).  ``decay``
+    may be an ``ops.ema.EMA`` (``num_updates`` is then its own): a caller that applies it every
+    step validates once and passes the object."""
+    from . import ema as ema_mod
+
+    e = decay if isinstance(decay, ema_mod.EMA) else ema_mod.EMA(decay, num_updates)
+    if shadow.numel() != p.numel():
+        raise ValueError("ema_: shadow and p must have the same number of elements")
+    if not shadow.is_cuda:
+        with torch.no_grad():
+            t = int(step if step_tensor is None else step_tensor.item())
+            shadow.sub_(shadow - p, alpha=float(e.one_minus_decay_f32(t)))
+        return shadow
+    check_gpu_f32(shadow, p)
+    if step_tensor is not None and step_tensor.dtype != torch.int32:
+        raise TypeError("step_tensor must be int32")
+    omd, nu = e.words()
+    hip().ema(shadow.numel(), ptr(shadow), ptr(p), omd, bool(nu), int(step), ptr(step_tensor),
+              stream_handle())
+    return shadow
+
+
 def scale_(x, a):
     if not x.is_cuda:
         x.mul_(a)

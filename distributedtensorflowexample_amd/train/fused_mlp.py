@@ -112,6 +112,25 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   exchange engines, the persistent launch, ``DTFX_MLP_KS=14`` and the fused flush have sigmoid
   heads only and refuse another activation.  ``activation="sigmoid"`` launches exactly today's
   kernels.
+* ``ema_decay`` / ``ema_num_updates`` (``--ema_decay``, ``--ema_num_updates``; ``ops/ema.py`` has
+  the definition, which is ``tf.train.ExponentialMovingAverage``'s): a shadow plane (``ema``: flat
+  f32 [79510] in the parameter layout, initialised from ``params`` at construction) follows the
+  parameters, ``shadow -= (1 - d_t) * (shadow - p_new)`` after every update, inside the first
+  launch: the lane that stores a new parameter value also reads and rewrites its shadow value,
+  exactly as it does its slot values (``mlp_lean_fwdapply_ema``: one instantiation per optimizer,
+  at a constant and at a scheduled rate, with or without decay; plain sgd takes it too, with the
+  step pair).  No launch and no gradient buffer is added; ``apply == 0`` touches no shadow byte;
+  the shadow never feeds back into training (parameters and slots are bit-identical to
+  ``ema_decay=0``).  With ``ema_num_updates`` ``d_t = min(decay, (1 + t) / (10 + t))`` comes from
+  the step word, once per wave, so ``seek`` restores it and leaves the shadow alone.
+  ``load_params`` does NOT reset the shadow (``load_ema`` sets it; a restore without averaged
+  variables calls ``load_ema(params)``).  ``snapshot(with_ema=True)`` and ``evaluate(ema=True)``
+  return / evaluate the shadow after every step run so far.  Works with every optimizer,
+  schedule, decay, shuffle, dropout and activation through ``step()``, graph replay,
+  ``run_launched``, ``flush``, ``seek`` and the all-reduce engine (``ops.optim.ema_`` after the
+  optimizer; sgd then applies in place).  The exchange engines, the three-launch direct step, the
+  persistent launch, ``DTFX_MLP_KS=14`` and the fused flush refuse it.  ``ema_decay=0`` launches
+  exactly today's kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -126,6 +145,7 @@ import time
 import torch
 
 from ..ops import dropout as dropout_mod
+from ..ops import ema as ema_mod
 from ..ops import hidden_act
 from ..ops import lr_schedule as lr_schedule_mod
 from ..ops import mlp_step, optim
@@ -140,7 +160,24 @@ class FusedMLPTrainer:
                  fused_comm=None, factor_comm=None, x_all=None, rank=0, pipeline=True,
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
                  beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0,
-                 weight_decay=0.0, adamw=True, nesterov=False, activation="sigmoid"):
+                 weight_decay=0.0, adamw=True, nesterov=False, activation="sigmoid",
+                 ema_decay=0.0, ema_num_updates=False):
+        # --ema_decay: refused first where no launch carries a shadow plane
+        self.avg = ema_mod.resolve(ema_decay, ema_num_updates)
+        if self.avg is not None:
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("ema_decay: the exchange engines (fused_comm / factor_comm) keep "
+                                 "no moving average of the parameters; use the all-reduce engine")
+            if not pipeline and allreduce is None and int(world_size) == 1:
+                raise ValueError("ema_decay: the three-launch direct step (pipeline=False) has "
+                                 "no moving-average variant; use the two-launch step "
+                                 "(pipeline=True)")
+            if params.is_cuda and allreduce is None and int(world_size) == 1:
+                from ..ops._ext import hip
+
+                if hip().mlp_single_ks() != 28:
+                    raise ValueError("ema_decay: DTFX_MLP_KS=14 has no moving-average variant; "
+                                     "use the default K slicing")
         # --activation: refused first where only the sigmoid head exists
         self.activation = hidden_act.check(activation)
         if self.activation != "sigmoid":
@@ -261,11 +298,15 @@ class FusedMLPTrainer:
         # lr_schedule: the same object also carries the schedule block and the rate ring, and
         # exists for scheduled sgd too (no slot plane) -- the scheduled step is an OptArgs one
         self.opt = None
-        if self.optimizer != "sgd" or self.sched is not None or self.decay is not None:
+        # ema_decay: it owns the shadow plane too, plain sgd included
+        if (self.optimizer != "sgd" or self.sched is not None or self.decay is not None
+                or self.avg is not None):
             self.opt = mlp_step.PipelinedOpt(self.optimizer, self.device, momentum, beta1, beta2,
                                              epsilon, schedule=self.sched, stats_ring=stats_ring,
-                                             decay=self.decay)
+                                             decay=self.decay, ema=self.avg)
             self.opt.set_step(global_step)
+            if self.avg is not None:
+                self.opt.shadow.copy_(self.bufs[0])  # shadow_0: the initial parameters, as in TF
         # the all-reduce engine's scheduled rate (ops.optim's lr_tensor)
         self._lr_dev = (torch.zeros(1, device=self.device, dtype=torch.float32)
                         if self.sched is not None else None)
@@ -333,17 +374,34 @@ class FusedMLPTrainer:
         self.pending = False
 
     @property
+    def ema(self):
+        """The moving average of the parameters (the shadow plane: flat f32 [79510] in the
+        parameter layout) -- like ``params`` and ``slots``, without a pending update."""
+        self._verified()
+        if self.avg is None:
+            raise RuntimeError("ema: the trainer keeps no moving average (ema_decay is 0)")
+        return self.opt.shadow
+
+    def load_ema(self, plane):
+        """Set the shadow plane (a restored checkpoint's averaged variables, or the restored
+        parameters when it has none); as ``load_slots``, nothing is pending afterwards."""
+        self.ema.copy_(plane.reshape(-1))
+        self.pending = False
+
+    @property
     def _inplace(self):
         """All-reduce engine with an optimizer: the reduced gradient is applied in place on the
         current buffer (``ops.optim``), so the parity never moves."""
         return self.opt is not None and not self.pipelined
 
-    def _apply_reduced(self, p, slots, publish=True):
+    def _apply_reduced(self, p, slots, publish=True, shadow=None):
         """The pending all-reduced gradient through the optimizer, in place on ``p`` /
         ``slots`` (graph-capturable: Adam's t is the device counter, which the step that
         produced the gradient already advanced to its ``global_step + 1``).  With a schedule
         the pending step's rate -- step ``counter - 1`` -- is computed on the device first and
-        read by the optimizer kernel (``publish``: also written to the rate ring)."""
+        read by the optimizer kernel (``publish``: also written to the rate ring).  With a
+        moving average ``shadow`` (default: the trainer's own) then follows the new ``p``
+        (``ops.optim.ema_``; its t is the same counter)."""
         optim.scale_(self.grad, 1.0 / self.world_size)
         h = self.opt.hyper
         lrt = None
@@ -359,6 +417,9 @@ class FusedMLPTrainer:
             kw = d.adam_kw if d else dict(weight_decay=0.0, adamw=False)
             optim.adam_(p, self.grad, slots[0], slots[1], self.lr, 0, beta1=h[0], beta2=h[1],
                         eps=h[2], step_tensor=self.ws.ctr, lr_tensor=lrt, **kw)
+        if self.avg is not None:
+            optim.ema_(self.opt.shadow if shadow is None else shadow, p, self.avg,
+                       step_tensor=self.ws.ctr)
 
     def flush(self):
         """Apply the pending update in place (DP: p -= lr/N * grad; pipelined: the last
@@ -391,10 +452,12 @@ class FusedMLPTrainer:
             self.pending = False
         return self.bufs[self.cur]
 
-    def snapshot(self, with_slots=False):
+    def snapshot(self, with_slots=False, with_ema=False):
         """``with_slots``: ``(parameters, [slot planes])`` instead, the slots by the same rules
         (new tensors; an optimizer's pending all-reduced gradient is applied to copies of the
-        parameters AND the slots, so the trainer's state does not move).
+        parameters AND the slots, so the trainer's state does not move).  ``with_ema``: the
+        shadow plane after every step run so far is appended, by the same rules -- ``(parameters,
+        shadow)``, or ``(parameters, [slot planes], shadow)`` with both.
 
         Parameters after every step run so far (a pending update included) as a NEW
         tensor, WITHOUT changing the trainer: no peer exchange starts and the replicas' update
@@ -403,15 +466,22 @@ class FusedMLPTrainer:
         copy.  A pending update of the pipelined exchange engines needs every rank's
         exchange: raises (call flush() on every rank instead)."""
         self._verified()
-        if with_slots:
+        if with_ema and self.avg is None:
+            raise RuntimeError("snapshot(with_ema=True): the trainer keeps no moving average "
+                               "(ema_decay is 0)")
+        if with_slots or with_ema:
             if self.pending and self._inplace:
                 out, sl = self.bufs[self.cur].clone(), [t.clone() for t in self.opt.slots]
+                sh = self.opt.shadow.clone() if self.avg is not None else None
                 g = self.grad.clone()  # (_apply_reduced scales the gradient in place)
-                self._apply_reduced(out, sl, publish=False)  # (the rate ring does not move)
+                # (the rate ring and the trainer's shadow do not move)
+                self._apply_reduced(out, sl, publish=False, shadow=sh)
                 self.grad.copy_(g)
-                return out, sl
-            out = self.snapshot()  # (pipelined on one GPU: flushed; slots then current)
-            return out, [t.clone() for t in self.slots]
+            else:
+                out = self.snapshot()  # (pipelined on one GPU: flushed; slots then current)
+                sl = [t.clone() for t in self.slots]
+                sh = self.opt.shadow.clone() if with_ema else None
+            return (out,) + ((sl,) if with_slots else ()) + ((sh,) if with_ema else ())
         p = self.bufs[self.cur]
         if not self.pending:
             return p.clone()
@@ -426,19 +496,25 @@ class FusedMLPTrainer:
         raise RuntimeError("snapshot(): the pending update is a peer exchange; flush() on "
                            "every rank first")
 
-    def evaluate(self, x, labels=None, **kw):
+    def evaluate(self, x, labels=None, ema=False, **kw):
         """``ops.mlp_eval.evaluate`` of the parameters after every step run so far on ``x``
         [n, 784] / ``labels`` (int32 [n]): one fused launch, no host synchronisation; the
         keyword arguments (``predictions``, ``probs``, ``acc``) are the op's.  The parameters
         are ``snapshot()``'s, by its rules: a pending pipelined update on one GPU is flushed,
         the all-reduce engine's pending gradient is applied to a copy, a pending peer exchange
-        raises.  ``global_step()`` is unchanged.  The hidden activation is the trainer's."""
+        raises.  ``global_step()`` is unchanged.  The hidden activation is the trainer's.
+        ``ema=True``: the moving average of the parameters (``snapshot(with_ema=True)``'s
+        shadow) is evaluated instead."""
         from ..ops import mlp_eval
 
         kw.setdefault("activation", self.activation)
-        return mlp_eval.evaluate(self.snapshot(), x, labels, **kw)
+        p = self.snapshot(with_ema=True)[1] if ema else self.snapshot()
+        return mlp_eval.evaluate(p, x, labels, **kw)
 
     def load_params(self, p):
+        """Set the parameters; nothing is pending afterwards.  The moving average is NOT reset:
+        a restore sets it with ``load_ema`` (the checkpoint's averaged variables, or these
+        parameters when it has none)."""
         self.bufs[self.cur].copy_(p)
         self.pending = False
 
@@ -646,13 +722,17 @@ class FusedMLPTrainer:
         if self.decay is not None and flush and _flush_fused():
             raise ValueError("weight_decay / nesterov: the fused flush (DTFX_MLP_FLUSH_FUSED) has "
                              "no weight-decay variant; flush in its own launch")
+        if self.avg is not None and flush and _flush_fused():
+            raise ValueError("ema_decay: the fused flush (DTFX_MLP_FLUSH_FUSED) has no "
+                             "moving-average variant; flush in its own launch")
         a = self._host_args
         if a is None:
             from ..ops._ext import hip, ptr
 
             ws = self.ws
             if self.opt is not None:  # the optimizer form of the plan (slot pointers bound too)
-                oargs = (self.opt.wd_args() if self.decay is not None
+                oargs = (self.opt.ema_args() if self.avg is not None
+                         else self.opt.wd_args() if self.decay is not None
                          else self.opt.args() if self.sched is None else self.opt.sched_args())
                 plan = hip().MlpRunOptPlan(ptr(self.bufs[0]), ptr(self.bufs[1]), ptr(self.x),
                                            ptr(self.labels), self.nbatches, ptr(ws.buf),
@@ -769,6 +849,10 @@ class FusedMLPTrainer:
         if self.decay is not None:
             raise ValueError("run_persistent: the persistent launch has no weight-decay or "
                              "Nesterov variant; use run() / run_launched()")
+        if self.avg is not None:
+            raise ValueError("run_persistent: the persistent launch keeps no moving average of "
+                             "the parameters (ema_decay is not supported); use run() / "
+                             "run_launched()")
         if not self.persistent_ok:
             raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
                                "(shuffle off, optimizer sgd)")

@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from ..models import mlp as mlp_model
 from ..ops import dropout as dropout_mod
+from ..ops import ema as ema_mod
 from ..ops import hidden_act
 from ..ops import lr_schedule, mlp_step, nn, optim
 from ..ops import weight_decay as weight_decay_mod
@@ -91,6 +92,17 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     # --activation: the hidden activation of the fused step's head, the evaluation kernel and the
     # autograd path (ops/hidden_act.py); a checkpoint does not record it
     act = hidden_act.from_flags(flags)
+    # --ema_decay / --ema_num_updates: the shadow plane inside the fused step's first launch / the
+    # all-reduce engine's ops.optim.ema_ call (train/fused_mlp.py), the same op on the autograd
+    # path; checkpoints carry the shadows as <variable>/ExponentialMovingAverage.  --eval_ema: the
+    # periodic test evaluation reads them
+    avg = ema_mod.from_flags(flags)
+    # (main.py validates the flags once for the CLI; this guard is for callers that embed
+    # train_mirrored with their own namespace, as the sibling guards above: the sharded update
+    # below would otherwise train without ever touching the shadow)
+    if avg is not None and getattr(flags, "zero1", False):
+        ema_mod.refuse(flags, "--zero1 (the sharded update)")
+    eval_ema = bool(getattr(flags, "eval_ema", False))
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -147,11 +159,12 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
                 and opt_kind == "sgd" and sched is None and drop is None and decay is None
-                and act == "sigmoid"):
+                and act == "sigmoid" and avg is None):
             # exchange engine (fused into the backward kernel / factor all-gather) when
             # verified and faster than the all-reduce engine (sgd at a constant rate without
             # dropout or weight decay and the sigmoid head only: with an optimizer, a schedule,
-            # --dropout, --weight_decay or --activation relu | tanh the all-reduce engine it is)
+            # --dropout, --weight_decay, --activation relu | tanh or --ema_decay the all-reduce
+            # engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -177,14 +190,17 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              weight_decay=decay.wd if decay else 0.0,
                              adamw=decay.adamw if decay else True,
                              nesterov=decay.nesterov if decay else False, activation=act,
-                             **opt_kw)
+                             ema_decay=avg.decay if avg else 0.0,
+                             ema_num_updates=avg.num_updates if avg else False, **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
         # eval / replica-check points, because the loop below reads each chunk's stats on
         # EVERY rank (stats_range flushes there, collectively)
         get_params = tr.snapshot
-        get_state = lambda: tr.snapshot(with_slots=True)  # noqa: E731
+        # (parameters, [slot planes], shadow plane or None)
+        get_state = lambda: (tr.snapshot(with_slots=True, with_ema=True) if avg is not None  # noqa: E731
+                             else tr.snapshot(with_slots=True) + (None,))
         step_fn = None
     else:
         model = mlp_model.MnistMLP(flat=params, activation=act)
@@ -196,7 +212,9 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         get_params = lambda: model.flat.detach().clone()  # noqa: E731
         cpu_slots = [torch.zeros(mlp_step.NPARAM)
                      for _ in range(gpu_ps_optim.num_slots(opt_kind))]
-        get_state = lambda: (get_params(), [t.clone() for t in cpu_slots])  # noqa: E731
+        cpu_shadow = model.flat.detach().clone() if avg is not None else None  # shadow_0 = p_0
+        get_state = lambda: (get_params(), [t.clone() for t in cpu_slots],  # noqa: E731
+                             None if cpu_shadow is None else cpu_shadow.clone())
 
         def step_fn():
             i = state["pos"]
@@ -246,6 +264,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                                    else dict(weight_decay=0.0, adamw=False)))
                 else:
                     optim.sgd_(model.flat.data, g, lr, **(decay.sgd_kw if decay else {}))
+                if avg is not None:  # after the update; t = global_step + 1 of this step
+                    optim.ema_(cpu_shadow, model.flat.data, avg, step=i + 1)
             return float(loss), float(acc)
 
     # one name tuple per slot plane, kernels in TF layout like the variables themselves
@@ -253,12 +273,19 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     var_names = (list(REFERENCE_MLP_NAMES) + [n for names in slot_names for n in names]
                  + ["global/global_step"])
     saver = FastSaver({n: None for n in var_names})
+    # the averaged variables under TF's names (kernels in TF layout like the variables); not in
+    # the saver's var list, which is what a restore REQUIRES: a checkpoint without them (a run
+    # without --ema_decay) restores, and the shadow then starts at the restored parameters
+    ema_names = tuple(ema_mod.tf_name(n) for n in REFERENCE_MLP_NAMES) if avg is not None else ()
 
     def save_vars():
-        p, slots = get_state()
+        p, slots, shadow = get_state()
         v = {k: t.contiguous() for k, t in flat_to_tf_vars(p.cpu()).items()}
         for names, plane in zip(slot_names, slots):
             v.update({k: t.contiguous() for k, t in flat_to_tf_vars(plane.cpu(), names).items()})
+        if shadow is not None:
+            v.update({k: t.contiguous()
+                      for k, t in flat_to_tf_vars(shadow.cpu(), ema_names).items()})
         v["global/global_step"] = torch.tensor(global_step(), dtype=torch.int32)
         return v
 
@@ -276,19 +303,27 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         # as TF's restore and the GPU parameter store's path do)
         planes = [tf_vars_to_flat(values, torch.zeros(mlp_step.NPARAM), names)
                   for names in slot_names]
+        shadow = None
+        if avg is not None:  # the checkpoint's shadows, or the restored parameters
+            shadow = (tf_vars_to_flat(values, torch.zeros(mlp_step.NPARAM), ema_names)
+                      if all(n in values for n in ema_names) else p.clone())
         if use_gpu:
             tr.load_params(p.to(dev))
             tr.load_slots([t.to(dev) for t in planes])
+            if shadow is not None:
+                tr.load_ema(shadow.to(dev))
             tr.seek(int(values["global/global_step"]))
         else:
             model.flat.data.copy_(p)
             for d, t in zip(cpu_slots, planes):
                 d.copy_(t)
+            if shadow is not None:
+                cpu_shadow.copy_(shadow)
             state["pos"] = int(values["global/global_step"])
         state["step"] = int(values["global/global_step"])
 
     # (the var list only: an sgd run restoring a momentum / Adam checkpoint ignores the slots)
-    saver.assign = restricted_assign(restore, var_names)
+    saver.assign = restricted_assign(restore, var_names + list(ema_names))
     # checkpoints are taken by the training loop between chunks (Supervisor.service): the
     # fused trainer's deferred update may only be flushed where every rank flushes it
     sv = Supervisor(is_chief=is_chief, logdir=flags.logdir if is_chief else None,
@@ -308,9 +343,9 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         (ops/mlp_eval.py) through the trainer; the CPU autograd path keeps the generic
         forward (and computes the loss only where --eval_summaries asks for it)."""
         if use_gpu:
-            res = tr.evaluate(test_x, test_y_dev)
+            res = tr.evaluate(test_x, test_y_dev, ema=eval_ema)
             return float(res.accuracy), float(res.loss)
-        p = get_params()
+        p = cpu_shadow.clone() if eval_ema else get_params()
         W1t, b1, W2t, b2 = mlp_step.unflatten(p)
         if act == "tanh":  # (not an epilogue of the generic GEMM)
             h = torch.tanh(nn.gemm(test_x, W1t, trans_b=True, bias=b1))
@@ -340,17 +375,24 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
             dist.broadcast(s, 0)
             s = int(s.item())
             planes = [t.clone() for t in (tr.slots if use_gpu else cpu_slots)]
+            if avg is not None:  # (... and its shadow plane, with the slots)
+                planes.append((tr.ema if use_gpu else cpu_shadow).clone())
             if comm is not None:  # (a restored chief's slot planes)
                 for t in planes:
                     comm.broadcast_(t, 0)
+            shadow = planes.pop() if avg is not None else None
             if use_gpu:
                 tr.load_params(p)
                 tr.load_slots(planes)
+                if shadow is not None:
+                    tr.load_ema(shadow)
                 tr.seek(s)
             else:
                 model.flat.data.copy_(p)
                 for d, t in zip(cpu_slots, planes):
                     d.copy_(t)
+                if shadow is not None:
+                    cpu_shadow.copy_(shadow)
                 state["pos"] = s
         chunk = int(flags.log_every)
         state["step"] = global_step()

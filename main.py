@@ -122,6 +122,19 @@ def main(argv=None):
         weight_decay.from_flags(FLAGS)
     except ValueError as e:
         raise SystemExit(str(e))
+    # --ema_decay / --ema_num_updates / --eval_ema: the mirrored MLP's parameters only (ops/ema.py)
+    from distributedtensorflowexample_amd.ops import ema
+
+    try:
+        if FLAGS.strategy != "mirrored":
+            ema.refuse(FLAGS, "--strategy ps_async (--ps_device cpu and gpu)")
+        elif FLAGS.model != "mlp":
+            ema.refuse(FLAGS, "--model %s" % FLAGS.model)
+        elif getattr(FLAGS, "zero1", False):
+            ema.refuse(FLAGS, "--zero1 (the sharded update)")
+        ema.from_flags(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if FLAGS.strategy == "mirrored" and FLAGS.model != "mlp":
         from distributedtensorflowexample_amd.train.mirrored_mlp import shutdown_mirrored
         from distributedtensorflowexample_amd.train.mirrored_models import train_model_mirrored
