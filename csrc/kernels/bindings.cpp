@@ -502,6 +502,27 @@ PYBIND11_MODULE(_hip, m) {
   m.def("mlp_eval_row_tile", &dtfx::mlp_eval_row_tile, "rows per workgroup of mlp_eval");
   m.def("mlp_eval_max_rows", &dtfx::mlp_eval_max_rows,
         "largest n of mlp_eval (the fixed-point loss sum cannot overflow up to it)");
+  // The large-batch gradient (csrc/kernels/mlp_large_batch.hip; ops/mlp_large_batch.py)
+  m.def("mlp_lb_workspace_floats", &dtfx::mlp_lb_workspace_floats,
+        "floats of the large-batch workspace for batch B (its last 4 words: the hand-off words)");
+  m.def("mlp_lb_slices", [](int B) {
+    int ns = 0, nr = 0;
+    dtfx::mlp_lb_slices(B, &ns, &nr);
+    return py::make_tuple(ns, nr);
+  }, "(S, R): the split-K slicing of the large-batch weight gradient, S slices of R rows");
+  m.def("mlp_lb_fwdhead", [](uintptr_t p, uintptr_t x, uintptr_t lab, uintptr_t ws, int B, int act,
+                             uintptr_t s) {
+    dtfx::mlp_lb_fwdhead_launch(P<const float>(p), P<const float>(x), P<const int>(lab),
+                                P<float>(ws), B, act, S(s));
+  }, "rows -> factors: h, dz1, dlogits and per-row (loss, correct) of B rows, row-major in ws");
+  m.def("mlp_lb_wgrad", [](uintptr_t x, uintptr_t ws, int B, uintptr_t s) {
+    dtfx::mlp_lb_wgrad_launch(P<const float>(x), P<float>(ws), B, S(s));
+  }, "factors -> one partial gradient plane per batch slice");
+  m.def("mlp_lb_reduce", [](uintptr_t ws, uintptr_t grad, uintptr_t ctr, uintptr_t stats, int ring,
+                            int B, uintptr_t s) {
+    dtfx::mlp_lb_reduce_launch(P<const float>(ws), P<float>(grad), P<int>(ctr), P<float>(stats),
+                               ring, B, S(s));
+  }, "planes -> flat gradient [79510] (slice order), stats[global_step % ring], global_step += 1");
   m.def("calib", [](int mode, int grid, int block, uintptr_t ctr, uintptr_t data, uintptr_t out,
                     uintptr_t s) {
     dtfx::calib_launch(mode, grid, block, P<const int>(ctr), P<const float>(data), P<float>(out),

@@ -167,4 +167,17 @@ int mlp_eval_max_rows();
 void mlp_eval_launch(const float* p, const float* x, const int* labels, int n, void* acc, int* pred,
                      float* probs, hipStream_t stream, int act = kMlpActSigmoid);
 
+// ---- the large-batch gradient (mlp_large_batch.hip): 257 <= B <= 65,536, three launches that
+// leave the flat gradient of the batch mean loss in `grad`, the step's loss / accuracy in the
+// stats ring and global_step advanced (mlp_wgrad's grad-mode contract).  ws: a zero-initialised
+// workspace of mlp_lb_workspace_floats(B) floats; mlp_lb_slices: the split-K slicing (S slices of
+// R rows).  Every function throws std::runtime_error outside the batch range.
+long long mlp_lb_workspace_floats(int B);
+void mlp_lb_slices(int B, int* S, int* R);
+void mlp_lb_fwdhead_launch(const float* p, const float* x, const int* labels, float* ws, int B,
+                           int act, hipStream_t stream);
+void mlp_lb_wgrad_launch(const float* x, float* ws, int B, hipStream_t stream);
+void mlp_lb_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
+                          int B, hipStream_t stream);
+
 }  // namespace dtfx

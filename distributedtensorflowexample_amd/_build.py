@@ -38,7 +38,10 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 # Per-file hipcc flags.  mlp_step.hip: up to 16 kernel-argument dwords are preloaded into user
 # SGPRs at wave launch (scalar and pointer arguments only; the lean step's kernels take nothing
 # else).  The compiler also emits the prologue for firmware that does not preload.
-HIP_FILE_FLAGS = {"mlp_step.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
+HIP_FILE_FLAGS = {"mlp_step.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
+                  # no packed-f32 VALU forms in this file's kernels (scalar f32 adds and MFMA only)
+                  "mlp_large_batch.hip": ["-Xclang", "-target-feature", "-Xclang",
+                                          "-packed-fp32-ops"]}
 
 
 def _pybind_includes():

@@ -165,7 +165,9 @@ def define_reference_flags(flag_values=FLAGS):
         return fv
     DEFINE_string("job_name", "ps", "Either 'ps' or 'worker'", fv)
     DEFINE_integer("task_index", 0, "Index of task within the job", fv)
-    DEFINE_integer("batch_size", 100, "Batch size", fv)
+    DEFINE_integer("batch_size", 100, "Batch size (the fused GPU MLP step: up to 256 in its "
+                   "two-launch form, 257..65536 through the large-batch gradient kernels, "
+                   "mirrored strategy, without --dropout)", fv)
     DEFINE_float("learning_rate", 0.001, "Learning rate", fv)
     DEFINE_integer("training_steps", 10 ** 7, "Training steps (1step = 1batch update", fv)
     DEFINE_string("logdir", "./tmp/mnist/1", "Log directory", fv)

@@ -131,6 +131,18 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   optimizer; sgd then applies in place).  The exchange engines, the three-launch direct step, the
   persistent launch, ``DTFX_MLP_KS=14`` and the fused flush refuse it.  ``ema_decay=0`` launches
   exactly today's kernels.
+* ``batch_size > 256`` (up to 65,536; ``ops/mlp_large_batch.py``): the large-batch engine.  The
+  launches above are shaped for at most 256 rows; beyond that the step is a pair of real GEMMs
+  and runs as the three launches of ``csrc/kernels/mlp_large_batch.hip``, which leave the flat
+  gradient.  The trainer then IS the all-reduce engine on any number of GPUs, one included
+  (``pipelined`` and ``direct`` are false): each step applies the pending gradient in place
+  through ``ops.optim`` -- every optimizer, schedule, decay and moving-average option; plain sgd
+  too, so the parity never moves -- then computes the next gradient and calls ``allreduce`` if
+  given.  ``flush``, ``snapshot``, ``stats``, ``seek``, ``evaluate``, ``shuffle`` and ``run()``'s
+  graph replays (one eager step first) work as they do for that engine.  ``dropout``,
+  ``fused_comm`` / ``factor_comm`` and a batch above 65,536 are refused in the constructor; the
+  C++ host loop and the persistent launch are not available.  ``batch_size <= 256`` launches
+  exactly today's kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -148,7 +160,7 @@ from ..ops import dropout as dropout_mod
 from ..ops import ema as ema_mod
 from ..ops import hidden_act
 from ..ops import lr_schedule as lr_schedule_mod
-from ..ops import mlp_step, optim
+from ..ops import mlp_large_batch, mlp_step, optim
 from ..ops import weight_decay as weight_decay_mod
 from ..ops._ext import stream_handle
 from ..parallel import gpu_ps_optim
@@ -245,6 +257,20 @@ class FusedMLPTrainer:
             if not pipeline and allreduce is None and int(world_size) == 1:
                 raise ValueError("optimizer %s: the three-launch direct step (pipeline=False) "
                                  "applies gradient descent only" % self.optimizer)
+        # batch_size > 256: the large-batch engine (module docstring), refused first where it
+        # has no variant
+        self.large = int(batch_size) > mlp_step.MAX_BATCH
+        if self.large:
+            if int(batch_size) > mlp_large_batch.MAX_LARGE_BATCH:
+                raise ValueError("batch_size %d: the large-batch step supports at most %d rows"
+                                 % (int(batch_size), mlp_large_batch.MAX_LARGE_BATCH))
+            if self.drop is not None:
+                raise ValueError("dropout: the large-batch step (batch_size > %d) has no dropout "
+                                 "variant yet" % mlp_step.MAX_BATCH)
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("fused_comm / factor_comm: the exchange engines support "
+                                 "batch_size <= %d; use the all-reduce engine"
+                                 % mlp_step.MAX_BATCH)
         if not params.is_cuda:
             raise ValueError("FusedMLPTrainer runs on the GPU; use the generic path on CPU")
         if params.numel() != mlp_step.NPARAM:
@@ -284,13 +310,15 @@ class FusedMLPTrainer:
         self.bufs = [params.detach().clone().contiguous(), torch.empty_like(params)]
         self.cur = 0
         self.grad = torch.zeros_like(params)
-        self.ws = mlp_step.StepWorkspace(self.B, self.device, stats_ring)
+        self.ws = (mlp_large_batch.LargeBatchWorkspace(self.B, self.device, stats_ring)
+                   if self.large else mlp_step.StepWorkspace(self.B, self.device, stats_ring))
         self.ws.set_global_step(global_step)
         self.pos = int(global_step) % self.nbatches  # next batch (host mirror)
         self.pending = False
         # single GPU without a communicator, the fused engine or the factor engine (batch
         # <= 128): the two-launch pipelined step
-        self.pipelined = bool(pipeline and allreduce is None and (
+        # (batch_size > 256: the large-batch engine is neither pipelined nor direct)
+        self.pipelined = bool(pipeline and not self.large and allreduce is None and (
             (self.world_size == 1 and factor_comm is None and fused_comm is None)
             or fused_comm is not None
             or (factor_comm is not None and self.B <= 128)))
@@ -337,7 +365,7 @@ class FusedMLPTrainer:
     @property
     def direct(self):
         """SGD apply fused into the backward kernel (one GPU, or the fused xGMI exchange)."""
-        return not self.pipelined and (
+        return not self.pipelined and not self.large and (
             self.fused_comm is not None or self.factor_comm is not None
             or (self.allreduce is None and self.world_size == 1))
 
@@ -627,7 +655,16 @@ class FusedMLPTrainer:
             self.pending = True
             return
         cur = self.bufs[self.cur]
-        if self.opt is not None:
+        if self.large:
+            # large-batch engine: the pending gradient in place (plain sgd as flush() does),
+            # then the three large-batch launches; the parity never moves
+            if self.pending and self.opt is not None:
+                self._apply_reduced(cur, self.opt.slots)
+            elif self.pending:
+                optim.sgd_(cur, self.grad, self.lr / self.world_size)
+            mlp_large_batch.step_grad(cur, xb, yb, self.ws, self.grad,
+                                      activation=self.activation)
+        elif self.opt is not None:
             # all-reduce engine with an optimizer: the reduced gradient of the previous step
             # through ops.optim in place, then the step without its deferred apply
             if self.pending:
@@ -907,7 +944,7 @@ class FusedMLPTrainer:
         for n in self._plan(steps):
             self._graph(n).replay()
             self.pos = (self.pos + n) % self.nbatches
-            if not self.direct and not self._inplace:
+            if not self.direct and not self._inplace and not self.large:
                 self.cur ^= n & 1
             if self.shuffle and self.pos == 0:  # the next epoch's gather, between two replays
                 self._wrapped()
@@ -928,7 +965,7 @@ class FusedMLPTrainer:
         for n in self._plan(steps):
             self._graph(n)
             self.pos = (self.pos + n) % self.nbatches
-            if not self.direct and not self._inplace:
+            if not self.direct and not self._inplace and not self.large:
                 self.cur ^= n & 1
             if self.shuffle and self.pos == 0:
                 self._bind(self.epoch + 1)  # (host mirrors only: which buffer the graph reads)

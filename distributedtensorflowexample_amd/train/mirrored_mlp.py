@@ -159,7 +159,7 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
                 and opt_kind == "sgd" and sched is None and drop is None and decay is None
-                and act == "sigmoid" and avg is None):
+                and act == "sigmoid" and avg is None and B <= mlp_step.MAX_BATCH):
             # exchange engine (fused into the backward kernel / factor all-gather) when
             # verified and faster than the all-reduce engine (sgd at a constant rate without
             # dropout or weight decay and the sigmoid head only: with an optimizer, a schedule,
