@@ -523,6 +523,32 @@ PYBIND11_MODULE(_hip, m) {
     dtfx::mlp_lb_reduce_launch(P<const float>(ws), P<float>(grad), P<int>(ctr), P<float>(stats),
                                ring, B, S(s));
   }, "planes -> flat gradient [79510] (slice order), stats[global_step % ring], global_step += 1");
+  // Its mixed-precision form (csrc/kernels/mlp_large_batch_bf16.hip): xh is the bf16 dataset
+  m.def("mlp_lbh_workspace_floats", &dtfx::mlp_lbh_workspace_floats,
+        "floats of the bf16 large-batch workspace for batch B (last 4 words: the hand-off words)");
+  m.def("mlp_lbh_slices", [](int B) {
+    int ns = 0, nr = 0;
+    dtfx::mlp_lbh_slices(B, &ns, &nr);
+    return py::make_tuple(ns, nr);
+  }, "(S, R): the split-K slicing of the bf16 weight gradient, S slices of R rows (R % 32 == 0)");
+  m.def("mlp_lbh_offsets", [](int B) {
+    long long o[8];
+    dtfx::mlp_lbh_offsets(B, o);
+    return py::make_tuple(o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
+  }, "float offsets of (h, dz1, dl, rowstat, bf16 dz1, planes) in the workspace, then BP, BP32");
+  m.def("mlp_lbh_fwdhead", [](uintptr_t p, uintptr_t xh, uintptr_t lab, uintptr_t ws, int B,
+                              int act, uintptr_t s) {
+    dtfx::mlp_lbh_fwdhead_launch(P<const float>(p), P<const unsigned short>(xh),
+                                 P<const int>(lab), P<float>(ws), B, act, S(s));
+  }, "bf16 rows -> factors: mlp_lb_fwdhead's f32 outputs plus dz1 as bf16 [BP32][112]");
+  m.def("mlp_lbh_wgrad", [](uintptr_t xh, uintptr_t ws, int B, uintptr_t s) {
+    dtfx::mlp_lbh_wgrad_launch(P<const unsigned short>(xh), P<float>(ws), B, S(s));
+  }, "bf16 factors -> one partial gradient plane per batch slice");
+  m.def("mlp_lbh_reduce", [](uintptr_t ws, uintptr_t grad, uintptr_t ctr, uintptr_t stats,
+                             int ring, int B, uintptr_t s) {
+    dtfx::mlp_lbh_reduce_launch(P<const float>(ws), P<float>(grad), P<int>(ctr), P<float>(stats),
+                                ring, B, S(s));
+  }, "mlp_lb_reduce on the bf16 workspace's planes");
   m.def("calib", [](int mode, int grid, int block, uintptr_t ctr, uintptr_t data, uintptr_t out,
                     uintptr_t s) {
     dtfx::calib_launch(mode, grid, block, P<const int>(ctr), P<const float>(data), P<float>(out),

@@ -50,8 +50,8 @@
 //     [slice][79,512] in the parameter layout (hidden rows 100..111 dropped); the two words
 //     behind b2 hold the slice's loss and correct sums.
 //
-// (c) mlp_lb_reduce: planes -> gradient.  One float4 per thread, the S planes added in slice
-//     order.  The thread of the last float4 (b2[8], b2[9], loss sum, correct sum) stores the two
+// (c) mlp_lb_reduce: planes -> gradient.  One float4 per thread, the S planes (pointer and count
+//     are arguments: mlp_large_batch_bf16.hip reduces its own planes with it) added in slice order.  The thread of the last float4 (b2[8], b2[9], loss sum, correct sum) stores the two
 //     gradient words and writes mean loss and accuracy to stats[global_step % stats_ring], then
 //     advances global_step: mlp_wgrad's contract (mlp_step_3launch.h), one thread, no other
 //     launch touches the counter.  Folding this launch into the optimizer kernels is left open.
@@ -444,18 +444,17 @@ __global__ __launch_bounds__(NW * 64) void mlp_lb_wgrad_kernel(const float* __re
 // ---------------------------------------------------------------------------
 // (c) planes -> gradient, stats record, global_step
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mlp_lb_reduce_kernel(const float* __restrict__ ws,
-                                                            float* __restrict__ grad,
+__global__ __launch_bounds__(256) void mlp_lb_reduce_kernel(const float* __restrict__ planes,
+                                                            int S, float* __restrict__ grad,
                                                             int* __restrict__ ctr,
                                                             float* __restrict__ stats,
                                                             int stats_ring, int B) {
-  const LbLayout L = lb_layout(B);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= NV4) return;
-  const float* src = ws + L.planes + (size_t)i * 4;
+  const float* src = planes + (size_t)i * 4;
   float4 v = f4(src);
 #pragma unroll 4
-  for (int s = 1; s < L.S; ++s) {  // slice order
+  for (int s = 1; s < S; ++s) {  // slice order
     const float4 u = f4(src + (size_t)s * PLANE);
     v.x += u.x;
     v.y += u.y;
@@ -528,8 +527,18 @@ void mlp_lb_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, 
                           int B, hipStream_t stream) {
   using namespace mlplb;
   check_batch("mlp_lb_reduce", B);
-  hipLaunchKernelGGL(mlp_lb_reduce_kernel, dim3((NV4 + 255) / 256), dim3(256), 0, stream, ws, grad,
-                     ctr, stats, stats_ring, B);
+  const LbLayout L = lb_layout(B);
+  mlp_lb_reduce_planes_launch(ws + L.planes, L.S, grad, ctr, stats, stats_ring, B, stream);
+}
+
+void mlp_lb_reduce_planes_launch(const float* planes, int S, float* grad, int* ctr, float* stats,
+                                 int stats_ring, int B, hipStream_t stream) {
+  using namespace mlplb;
+  check_batch("mlp_lb_reduce", B);
+  if (S < 1 || (reinterpret_cast<uintptr_t>(planes) & 15))
+    throw std::runtime_error("mlp_lb_reduce: needs S >= 1 planes at a 16-byte aligned address");
+  hipLaunchKernelGGL(mlp_lb_reduce_kernel, dim3((NV4 + 255) / 256), dim3(256), 0, stream, planes,
+                     S, grad, ctr, stats, stats_ring, B);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

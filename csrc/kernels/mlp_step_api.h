@@ -179,5 +179,22 @@ void mlp_lb_fwdhead_launch(const float* p, const float* x, const int* labels, fl
 void mlp_lb_wgrad_launch(const float* x, float* ws, int B, hipStream_t stream);
 void mlp_lb_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
                           int B, hipStream_t stream);
+// the same launch on S planes at `planes` (16-byte aligned): what mlp_lb_reduce_launch calls
+void mlp_lb_reduce_planes_launch(const float* planes, int S, float* grad, int* ctr, float* stats,
+                                 int stats_ring, int B, hipStream_t stream);
+
+// ---- its mixed-precision form (mlp_large_batch_bf16.hip): the same contract and batch range with
+// the dataset as row-major bf16 xh [n][784] (16-byte aligned) and the two 784-wide GEMMs on the
+// bf16 MFMA; the parameters stay f32.  ws: a zero-initialised workspace of
+// mlp_lbh_workspace_floats(B) floats (a layout of its own).  mlp_lbh_offsets fills off[8]: the
+// float offsets of h, dz1, dl, rowstat, the bf16 dz1 plane and the planes, then BP and BP32.
+long long mlp_lbh_workspace_floats(int B);
+void mlp_lbh_slices(int B, int* S, int* R);
+void mlp_lbh_offsets(int B, long long* off);
+void mlp_lbh_fwdhead_launch(const float* p, const unsigned short* xh, const int* labels, float* ws,
+                            int B, int act, hipStream_t stream);
+void mlp_lbh_wgrad_launch(const unsigned short* xh, float* ws, int B, hipStream_t stream);
+void mlp_lbh_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
+                           int B, hipStream_t stream);
 
 }  // namespace dtfx

@@ -41,7 +41,9 @@ EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 HIP_FILE_FLAGS = {"mlp_step.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"],
                   # no packed-f32 VALU forms in this file's kernels (scalar f32 adds and MFMA only)
                   "mlp_large_batch.hip": ["-Xclang", "-target-feature", "-Xclang",
-                                          "-packed-fp32-ops"]}
+                                          "-packed-fp32-ops"],
+                  "mlp_large_batch_bf16.hip": ["-Xclang", "-target-feature", "-Xclang",
+                                               "-packed-fp32-ops"]}
 
 
 def _pybind_includes():

@@ -167,7 +167,7 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_integer("task_index", 0, "Index of task within the job", fv)
     DEFINE_integer("batch_size", 100, "Batch size (the fused GPU MLP step: up to 256 in its "
                    "two-launch form, 257..65536 through the large-batch gradient kernels, "
-                   "mirrored strategy, without --dropout)", fv)
+                   "mirrored strategy, without --dropout; --dtype bf16 needs more than 256)", fv)
     DEFINE_float("learning_rate", 0.001, "Learning rate", fv)
     DEFINE_integer("training_steps", 10 ** 7, "Training steps (1step = 1batch update", fv)
     DEFINE_string("logdir", "./tmp/mnist/1", "Log directory", fv)
@@ -297,8 +297,10 @@ def define_reference_flags(flag_values=FLAGS):
                   fv)
     DEFINE_integer("seq_len", 128, "BERT sequence length", fv)
     DEFINE_integer("image_size", 224, "ResNet input resolution", fv)
-    DEFINE_string("dtype", "auto", "auto: fp32 for the MLP (reference dtype), bf16 for bert/resnet50",
-                  fv)
+    DEFINE_string("dtype", "auto", "auto: fp32 for the MLP (reference dtype), bf16 for bert/resnet50."
+                  "  bf16 with --model mlp (mirrored strategy, GPU, --batch_size > 256): bf16 "
+                  "operands and f32 accumulation in the large-batch step's two 784-wide GEMMs, f32 "
+                  "master weights; fp32: as auto for the MLP", fv)
     DEFINE_float("bucket_mb", 32.0, "All-reduce bucket size for generic DDP models (MiB)", fv)
     DEFINE_boolean("sync_replicas", False,
                    "ps_async strategy: aggregate each step's gradients over "

@@ -143,6 +143,15 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   ``fused_comm`` / ``factor_comm`` and a batch above 65,536 are refused in the constructor; the
   C++ host loop and the persistent launch are not available.  ``batch_size <= 256`` launches
   exactly today's kernels.
+* ``compute_dtype="bf16"`` (large-batch engine only; ``csrc/kernels/mlp_large_batch_bf16.hip``):
+  mixed precision.  The two 784-wide GEMMs of the step take bf16 operands on the bf16 MFMA and
+  accumulate in f32; the parameters stay the one f32 buffer (W1 is rounded on its way into the
+  MFMA), and the head, the small parameters, the gradient, the optimizers and ``evaluate`` are
+  f32 as before.  The trainer keeps a bf16 copy of each resident dataset buffer, made at
+  construction and, in shuffle mode, remade after every gather (a torch cast, once per epoch,
+  outside the step and the graphs); ``batch()`` returns its rows.  Everything the large-batch
+  engine supports works unchanged.  ``batch_size <= 256`` is latency-bound and gains nothing:
+  refused in the constructor.  ``compute_dtype="fp32"`` launches exactly today's kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -173,7 +182,7 @@ class FusedMLPTrainer:
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
                  beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0,
                  weight_decay=0.0, adamw=True, nesterov=False, activation="sigmoid",
-                 ema_decay=0.0, ema_num_updates=False):
+                 ema_decay=0.0, ema_num_updates=False, compute_dtype="fp32"):
         # --ema_decay: refused first where no launch carries a shadow plane
         self.avg = ema_mod.resolve(ema_decay, ema_num_updates)
         if self.avg is not None:
@@ -271,6 +280,14 @@ class FusedMLPTrainer:
                 raise ValueError("fused_comm / factor_comm: the exchange engines support "
                                  "batch_size <= %d; use the all-reduce engine"
                                  % mlp_step.MAX_BATCH)
+        # compute_dtype bf16: the large-batch engine's mixed-precision kernels only
+        if compute_dtype not in ("fp32", "bf16"):
+            raise ValueError("compute_dtype must be 'fp32' or 'bf16', got %r" % (compute_dtype,))
+        self.bf16 = compute_dtype == "bf16"
+        if self.bf16 and not self.large:
+            raise ValueError("compute_dtype bf16: only the large-batch step (batch_size > %d) has "
+                             "bf16 kernels; the step for up to %d rows is latency-bound and runs "
+                             "in fp32" % (mlp_step.MAX_BATCH, mlp_step.MAX_BATCH))
         if not params.is_cuda:
             raise ValueError("FusedMLPTrainer runs on the GPU; use the generic path on CPU")
         if params.numel() != mlp_step.NPARAM:
@@ -304,13 +321,15 @@ class FusedMLPTrainer:
         if self.nbatches < 1:
             raise ValueError("dataset smaller than one batch")
         self.x, self.labels = x, labels
+        self.xh = x.to(torch.bfloat16) if self.bf16 else None  # (round-to-nearest-even)
         self.shuffle = bool(shuffle)
         self.shuffle_seed = int(shuffle_seed)
         self.epoch = 0  # epoch of the next step (advanced in shuffle mode only)
         self.bufs = [params.detach().clone().contiguous(), torch.empty_like(params)]
         self.cur = 0
         self.grad = torch.zeros_like(params)
-        self.ws = (mlp_large_batch.LargeBatchWorkspace(self.B, self.device, stats_ring)
+        self.ws = (mlp_large_batch.LargeBatchWorkspace(self.B, self.device, stats_ring,
+                                                       bf16=self.bf16)
                    if self.large else mlp_step.StepWorkspace(self.B, self.device, stats_ring))
         self.ws.set_global_step(global_step)
         self.pos = int(global_step) % self.nbatches  # next batch (host mirror)
@@ -356,6 +375,9 @@ class FusedMLPTrainer:
             self._dst = [torch.empty_like(src), torch.empty_like(src)]
             self.xs = [d[int(rank)] if factor_comm is not None else d for d in self._dst]
             self.ys = [torch.empty_like(labels), torch.empty_like(labels)]
+            # compute_dtype bf16: one bf16 copy per shuffled buffer, refilled by _gather
+            self.xhs = [torch.empty_like(d, dtype=torch.bfloat16) if self.bf16 else None
+                        for d in self.xs]
             self._hargs = [None, None]
             self.run_launched = self._run_launched_epochs
             self._bind(int(global_step) // self.nbatches)
@@ -552,8 +574,10 @@ class FusedMLPTrainer:
         return self.ws.global_step() + (1 if (self.pipelined and self.pending) else 0)
 
     def batch(self, i):
+        """Rows and labels of batch ``i`` as the step reads them (compute_dtype bf16: the rows of
+        the bf16 copy)."""
         sl = slice(i * self.B, (i + 1) * self.B)
-        return self.x[sl], self.labels[sl]
+        return (self.xh if self.bf16 else self.x)[sl], self.labels[sl]
 
     def _xprev(self, pos):
         """The batch before position ``pos`` of the stream: the pending update's input.  In
@@ -571,6 +595,7 @@ class FusedMLPTrainer:
         self.epoch = int(epoch)
         k = self.epoch & 1
         self.x, self.labels, self._host_args = self.xs[k], self.ys[k], self._hargs[k]
+        self.xh = self.xhs[k]
 
     def _gather(self):
         """Write the current epoch's order into its buffer: position j <- original row
@@ -581,6 +606,8 @@ class FusedMLPTrainer:
         k = self.epoch & 1
         shuffle_rows_(self._dst[k], self.ys[k], self._src, self.labels0, self.shuffle_seed,
                       self.epoch)
+        if self.bf16:  # (once per epoch, in order on the compute stream, outside the graphs)
+            self.xhs[k].copy_(self.xs[k])
 
     def _wrapped(self):
         """After the step(s) that moved ``pos``: at an epoch boundary in shuffle mode, move to
@@ -662,8 +689,8 @@ class FusedMLPTrainer:
                 self._apply_reduced(cur, self.opt.slots)
             elif self.pending:
                 optim.sgd_(cur, self.grad, self.lr / self.world_size)
-            mlp_large_batch.step_grad(cur, xb, yb, self.ws, self.grad,
-                                      activation=self.activation)
+            (mlp_large_batch.step_grad_bf16 if self.bf16 else mlp_large_batch.step_grad)(
+                cur, xb, yb, self.ws, self.grad, activation=self.activation)
         elif self.opt is not None:
             # all-reduce engine with an optimizer: the reduced gradient of the previous step
             # through ops.optim in place, then the step without its deferred apply

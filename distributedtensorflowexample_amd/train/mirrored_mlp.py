@@ -97,6 +97,14 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     # path; checkpoints carry the shadows as <variable>/ExponentialMovingAverage.  --eval_ema: the
     # periodic test evaluation reads them
     avg = ema_mod.from_flags(flags)
+    # --dtype: auto | fp32 are the f32 step; bf16 is the fused trainer's mixed-precision large-batch
+    # step (FusedMLPTrainer(compute_dtype="bf16"), which refuses --batch_size <= 256)
+    dtype = getattr(flags, "dtype", "auto") or "auto"
+    if dtype not in ("auto", "fp32", "bf16"):
+        raise ValueError("--dtype: unknown value %r (auto | fp32 | bf16)" % (dtype,))
+    if dtype == "bf16" and not use_gpu:
+        raise ValueError("--dtype bf16: the MLP's bf16 step runs on the GPU only (--device cpu "
+                         "trains in fp32)")
     # (main.py validates the flags once for the CLI; this guard is for callers that embed
     # train_mirrored with their own namespace, as the sibling guards above: the sharded update
     # below would otherwise train without ever touching the shadow)
@@ -191,7 +199,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              adamw=decay.adamw if decay else True,
                              nesterov=decay.nesterov if decay else False, activation=act,
                              ema_decay=avg.decay if avg else 0.0,
-                             ema_num_updates=avg.num_updates if avg else False, **opt_kw)
+                             ema_num_updates=avg.num_updates if avg else False,
+                             compute_dtype="bf16" if dtype == "bf16" else "fp32", **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /

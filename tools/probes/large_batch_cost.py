@@ -6,7 +6,10 @@ In the same process, interleaved with it (>= 5 pairs per batch size), the only o
 such a batch: ``models.dense.DenseClassifier(hidden=(100,), activation="sigmoid").grads`` (the
 generic GEMM + autograd path, which reads loss and accuracy back every step) plus ``optim.sgd_``
 on every variable.  A timed window is sized to about ``--window`` seconds from a calibration run;
-both sides are warmed first.  Prints one JSON line.
+both sides are warmed first.  Above 256 rows a third trainer, ``compute_dtype="bf16"``
+(mlp_large_batch_bf16.hip), is interleaved with the two in the same windows: its figure is compared
+with the f32 engine of the same process only (``bf16_over_f32`` > 1: bf16 is slower).  Prints one
+JSON line.
 
     python tools/probes/large_batch_cost.py [--pairs 5] [--window 0.25]
     python tools/probes/large_batch_cost.py --trace_batch 1024   # only run(); for rocprofv3
@@ -68,13 +71,15 @@ def main():
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25)
     ap.add_argument("--trace_batch", type=int, default=0)
+    ap.add_argument("--trace_dtype", default="fp32", choices=["fp32", "bf16"])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     x, y = mnist_like_device(a.rows, seed=100, device=dev)
     y = y.int()
     p = init_params(dev, seed=0)
     if a.trace_batch:
-        tr = FusedMLPTrainer(p, x, y, batch_size=a.trace_batch, learning_rate=LR)
+        tr = FusedMLPTrainer(p, x, y, batch_size=a.trace_batch, learning_rate=LR,
+                             compute_dtype=a.trace_dtype)
         tr.run(8)
         tr.run(200)
         torch.cuda.synchronize()
@@ -84,14 +89,22 @@ def main():
     for B in (int(s) for s in a.sizes.split(",")):
         tr = FusedMLPTrainer(p, x, y, batch_size=B, learning_rate=LR)
         gen = Generic(p, x, y, B)
-        tr.run(1, use_graph=False)
-        tr.run(2 * tr.nbatches)  # every graph once
+        trh = (FusedMLPTrainer(p, x, y, batch_size=B, learning_rate=LR, compute_dtype="bf16")
+               if tr.large else None)
+        for t in (tr, trh):
+            if t is not None:
+                t.run(1, use_graph=False)
+                t.run(2 * t.nbatches)  # every graph once
         gen.run(5)
         k = {"fused": max(20, int(a.window * 1e6 / timed(tr.run, 50))),
              "generic": max(10, int(a.window * 1e6 / timed(gen.run, 10)))}
         us = {"fused": [], "generic": []}
+        if trh is not None:
+            k["fused_bf16"], us["fused_bf16"] = k["fused"], []
         for _ in range(a.pairs):
             us["fused"].append(timed(tr.run, k["fused"]))
+            if trh is not None:
+                us["fused_bf16"].append(timed(trh.run, k["fused_bf16"]))
             us["generic"].append(timed(gen.run, k["generic"]))
         med = {m: sorted(v)[len(v) // 2] for m, v in us.items()}
         rows.append({
@@ -103,6 +116,9 @@ def main():
             "generic_over_fused": round(med["generic"] / med["fused"], 2),
             "loss": {"fused": round(tr.stats()[0], 4), "generic": round(gen.loss, 4)},
         })
+        if trh is not None:
+            rows[-1]["bf16_over_f32"] = round(med["fused_bf16"] / med["fused"], 3)
+            rows[-1]["loss"]["fused_bf16"] = round(trh.stats()[0], 4)
     print(json.dumps({"rows": a.rows, "pairs": a.pairs, "sizes": rows}), flush=True)
 
 
