@@ -14,6 +14,7 @@
 #include <string>
 
 #include "f32_api.h"
+#include "mlp_model.h"
 #include "mlp_step_api.h"
 
 namespace py = pybind11;
@@ -26,6 +27,17 @@ void register_gpu_ps(py::module_& m);
 template <typename T>
 static inline T* P(uintptr_t a) { return reinterpret_cast<T*>(a); }
 static inline hipStream_t S(uintptr_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// A Python tuple of segment boundaries as the layer-wise launchers' table (validated there).
+static dtfx::LwSegs lw_segs(const py::tuple& offsets) {
+  long long off[dtfx::kLwMaxSegments + 1];
+  const size_t n = offsets.size();
+  if (n < 2 || n > (size_t)dtfx::kLwMaxSegments + 1)
+    throw std::runtime_error("layerwise: 1.." + std::to_string(dtfx::kLwMaxSegments) +
+                             " segments, got " + std::to_string((long long)n - 1));
+  for (size_t i = 0; i < n; ++i) off[i] = offsets[i].cast<long long>();
+  return dtfx::layerwise_segments(off, (int)n - 1);
+}
 
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "gfx950 HIP kernels of distributedtensorflowexample_amd";
@@ -459,6 +471,29 @@ PYBIND11_MODULE(_hip, m) {
                      P<const int>(step_ptr), S(s));
   }, "shadow -= (1 - d_t) * (shadow - p) in place (omd = 1 - decay; num_updates: d_t = "
      "min(decay, (1 + t) / (10 + t)), t = *step_ptr or step)");
+  // Layer-wise rules.  offsets: the segment boundaries (0, ..., n) as a tuple of ints; partials:
+  // the caller's 2 * layerwise_blocks(offsets) floats.
+  m.def("mlp_segments", []() {
+    namespace mm = dtfx::mlp_model;
+    return py::make_tuple(mm::OFF_W1, mm::OFF_B1, mm::OFF_W2, mm::OFF_B2, mm::NPARAM);
+  }, "the MLP's flat parameter layout (mlp_model.h) as segment boundaries: W1t, b1, W2t, b2");
+  m.def("layerwise_blocks", [](py::tuple offsets) {
+    return dtfx::layerwise_blocks(lw_segs(offsets));
+  }, "workgroups (pairs of partial sums) of a segment table; throws on a table the kernels "
+     "do not take");
+  m.def("lars", [](py::tuple offsets, uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t partials,
+                   float lr, uintptr_t lr_ptr, float mu, float eta, float wd, uintptr_t s) {
+    dtfx::lars_launch(lw_segs(offsets), P<float>(p), P<const float>(g), P<float>(v),
+                      P<float>(partials), lr, P<const float>(lr_ptr), mu, eta, wd, S(s));
+  }, "LARS in place: per-segment norms into partials, then momentum on r_k (g + wd p)");
+  m.def("lamb", [](py::tuple offsets, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v,
+                   uintptr_t partials, float lr, uintptr_t lr_ptr, double b1, double b2, float eps,
+                   float wd, int step, uintptr_t step_ptr, uintptr_t s) {
+    dtfx::lamb_launch(lw_segs(offsets), P<float>(p), P<const float>(g), P<float>(mm), P<float>(v),
+                      P<float>(partials), lr, P<const float>(lr_ptr), b1, b2, eps, wd, step,
+                      P<const int>(step_ptr), S(s));
+  }, "LAMB in place: m, v and per-segment norms of p and u into partials, then p -= lr r_k u "
+     "(t = *step_ptr or step)");
   m.def("scale", [](long long n, uintptr_t x, float a, uintptr_t s) {
     dtfx::scale_launch(n, P<float>(x), a, S(s));
   });

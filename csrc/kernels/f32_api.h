@@ -35,6 +35,23 @@ void adam_launch(long long n, float* p, const float* g, float* m, float* v, floa
                  const int* step_ptr, hipStream_t s);
 void ema_launch(long long n, float* shadow, const float* p, float omd, bool num_updates, int step,
                 const int* step_ptr, hipStream_t s);
+// Layer-wise rules (lars, lamb): the flat buffer cut into at most 8 segments, one per tensor.
+// off[k] .. off[k + 1] are segment k's elements, blk[k] .. blk[k + 1] its workgroups of 1,024
+// elements; passed to the kernels by value.  `partials`: the caller's 2 * layerwise_blocks()
+// floats (8-byte aligned), fully rewritten by every call.
+constexpr int kLwMaxSegments = 8;
+struct LwSegs {
+  int nseg;
+  int off[kLwMaxSegments + 1];
+  int blk[kLwMaxSegments + 1];
+};
+LwSegs layerwise_segments(const long long* offsets, int nseg);
+int layerwise_blocks(const LwSegs& sg);
+void lars_launch(const LwSegs& sg, float* p, const float* g, float* v, float* partials, float lr,
+                 const float* lr_ptr, float mu, float eta, float wd, hipStream_t s);
+void lamb_launch(const LwSegs& sg, float* p, const float* g, float* m, float* v, float* partials,
+                 float lr, const float* lr_ptr, double beta1, double beta2, float eps, float wd,
+                 int step, const int* step_ptr, hipStream_t s);
 void scale_launch(long long n, float* x, float a, hipStream_t s);
 void counter_add_launch(int* c, int d, hipStream_t s);
 void philox_init_launch(long long n, float* out, unsigned long long seed, unsigned long long offset,

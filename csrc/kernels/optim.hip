@@ -8,14 +8,18 @@
 //   scale    : x *= alpha                        (gradient averaging)
 //   ema      : shadow -= (1 - d_t) * (shadow - p) (tf.train.ExponentialMovingAverage;
 //                                                 ops/ema.py is the definition)
+//   lars     : momentum on g' = r_k (g + wd * p), r_k the segment's trust ratio
+//   lamb     : Adam's direction u, p -= lr * r_k * u   (two launches each, see below;
+//                                                 ops/layerwise.py is the definition)
 //
-// All loops are grid-stride over float4 (dwordx4) with a scalar tail.
+// The streaming loops are grid-stride over float4 (dwordx4) with a scalar tail.
 // `lr_ptr` / `step_ptr` (optional) let a captured hipGraph pick up a device-side
 // learning-rate schedule / step count instead of a frozen kernel argument.
 #include "common.h"
 #include "f32_api.h"
 #include "philox.h"
 
+#include <cmath>
 #include <stdexcept>
 
 namespace dtfx {
@@ -197,6 +201,305 @@ void scale_launch(long long n, float* x, float a, hipStream_t s) {
 
 void counter_add_launch(int* c, int d, hipStream_t s) {
   hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(64), 0, s, c, d);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Layer-wise adaptive rates: LARS and LAMB (ops/layerwise.py has the definition).
+//
+// Both rules need the Euclidean norm of every parameter tensor (a *segment* of the flat buffer)
+// between forming the update direction and applying it, so each is two launches over ONE
+// segment-aligned grid: a workgroup of 256 threads owns 1,024 consecutive elements (one float4 per
+// thread) of ONE segment -- segment k owns ceil(len_k / 1024) consecutive workgroups, none
+// straddles two segments, and a workgroup finds its segment by a wave-uniform scan of the (at
+// most 8) block-count prefixes in the by-value LwSegs.
+//
+//   launch 1 (norms): every thread squares its float4 of the two vectors whose norms the rule
+//     takes (lars: p, g; lamb: p, u -- lamb also writes the new m, v here), adds the four squares
+//     in element order, the wave adds its 64 lanes by the fixed DPP tree (wave_sum_n), the four
+//     waves meet in the LDS and are added in wave order, and thread 0 stores the pair to
+//     partials[block][2].  No atomics; elements past the segment's end contribute +0.
+//   launch 2 (apply): every WAVE of a workgroup adds its segment's partial pairs itself --
+//     lane-strided in block order, then the same fixed tree -- so the order is a function of the
+//     segment table alone, every wave of the segment sees the same bits, and no LDS or barrier is
+//     needed (the MLP's largest segment has 77 pairs: two 8-byte loads per lane, where a serial
+//     uniform loop is 77 dependent scalar loads).  It forms the trust ratio r_k once (f32 sqrtf,
+//     one division) and applies the update.  lamb recomputes u from the stored m, v and the
+//     still-unchanged p through lamb_u(), the function launch 1 used, so both launches see the
+//     same bits and no 318 KB scratch plane of u is written and read back.
+//
+// Launchers allocate nothing, clear nothing and never synchronise: `partials` is the caller's
+// (2 floats per workgroup), lr_ptr / step_ptr are read on the device as adam_kernel reads them,
+// and every result is bit-reproducible and graph-capturable.
+// ---------------------------------------------------------------------------
+constexpr int kLwBlock = 1024;  // elements per workgroup
+
+struct LwWork {   // what one thread owns
+  int seg;        // its segment
+  int blk0, blk1; // the segment's workgroups [blk0, blk1)
+  long long i;    // its first element
+  int nv;         // live elements of its float4: 0..4 (< 4 only at the buffer's ragged end)
+};
+
+__device__ __forceinline__ LwWork lw_work(const LwSegs& sg) {
+  const int b = blockIdx.x;
+  int k = 0;
+#pragma unroll
+  for (int i = 1; i < kLwMaxSegments; ++i)  // (uniform: blockIdx and kernel arguments only)
+    if (i < sg.nseg && b >= sg.blk[i]) k = i;
+  int off0 = sg.off[0], off1 = sg.off[1], blk0 = sg.blk[0], blk1 = sg.blk[1];
+#pragma unroll
+  for (int i = 1; i < kLwMaxSegments; ++i)  // (selects with constant indices: no private array)
+    if (k == i) { off0 = sg.off[i]; off1 = sg.off[i + 1]; blk0 = sg.blk[i]; blk1 = sg.blk[i + 1]; }
+  LwWork w;
+  w.seg = k;
+  w.blk0 = blk0;
+  w.blk1 = blk1;
+  w.i = (long long)off0 + (long long)(b - blk0) * kLwBlock + 4 * (int)threadIdx.x;
+  const long long left = (long long)off1 - w.i;
+  w.nv = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
+  return w;
+}
+
+// A thread's up-to-four values: one dwordx4 when whole, the scalar tail otherwise (dead lanes 0).
+__device__ __forceinline__ float4 lw_load(const float* __restrict__ x, const LwWork& w) {
+  if (w.nv == 4) return *reinterpret_cast<const float4*>(x + w.i);
+  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (w.nv > 0) r.x = x[w.i];
+  if (w.nv > 1) r.y = x[w.i + 1];
+  if (w.nv > 2) r.z = x[w.i + 2];
+  return r;
+}
+__device__ __forceinline__ void lw_store(float* __restrict__ x, const LwWork& w, float4 r) {
+  if (w.nv == 4) {
+    *reinterpret_cast<float4*>(x + w.i) = r;
+    return;
+  }
+  if (w.nv > 0) x[w.i] = r.x;
+  if (w.nv > 1) x[w.i + 1] = r.y;
+  if (w.nv > 2) x[w.i + 2] = r.z;
+}
+
+// Sum of squares of a thread's values, in element order (dead lanes are +0).
+__device__ __forceinline__ float lw_sq(float4 a) {
+  float s = a.x * a.x;
+  s = __fmaf_rn(a.y, a.y, s);
+  s = __fmaf_rn(a.z, a.z, s);
+  return __fmaf_rn(a.w, a.w, s);
+}
+
+// The workgroup's pair of sums -> partials[block][2]: DPP tree per wave, waves in wave order.
+__device__ __forceinline__ void lw_block_sums(float a, float b, float* __restrict__ partials) {
+  __shared__ float lds[4][2];
+  float s[2] = {a, b};
+  wave_sum_n(s);
+  const int wave = threadIdx.x >> 6;
+  if (lane_id() == 0) {
+    lds[wave][0] = s[0];
+    lds[wave][1] = s[1];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float s0 = ((lds[0][0] + lds[1][0]) + lds[2][0]) + lds[3][0];
+    const float s1 = ((lds[0][1] + lds[1][1]) + lds[2][1]) + lds[3][1];
+    *reinterpret_cast<float2*>(partials + 2 * (long long)blockIdx.x) = make_float2(s0, s1);
+  }
+}
+
+// The segment's pair of sums, in every lane of the calling wave: lane l adds the pairs of blocks
+// blk0 + l, blk0 + l + 64, ... in that order, then the fixed tree.
+__device__ __forceinline__ void lw_segment_sums(const float* __restrict__ partials,
+                                                const LwWork& w, float& a, float& b) {
+  float s[2] = {0.f, 0.f};
+  for (int j = w.blk0 + lane_id(); j < w.blk1; j += kWave) {
+    const float2 v = *reinterpret_cast<const float2*>(partials + 2 * (long long)j);
+    s[0] += v.x;
+    s[1] += v.y;
+  }
+  wave_sum_n(s);
+  a = s[0];
+  b = s[1];
+}
+
+// LAMB's bias corrections and update direction: ONE definition for both launches (explicit fma /
+// mul, so no contraction choice can differ between them).  lb = log(beta), rounded once from the
+// host's double: 1 - beta^t = -expm1(t log beta) keeps its relative accuracy at small t, where
+// 1.f - powf(0.999f, t) loses five digits to the rounding of beta -- a segment with r = 1 (no
+// norm to cancel a common factor of u) shows it.
+__device__ __forceinline__ void lamb_corr(float lb1, float lb2, int t, float& rbc1, float& rbc2) {
+  rbc1 = 1.f / -expm1f((float)t * lb1);
+  rbc2 = rsqrtf(-expm1f((float)t * lb2));
+}
+__device__ __forceinline__ float lamb_u(float p, float m, float v, float rbc1, float rbc2,
+                                        float eps, float wd) {
+  const float q = __fmul_rn(m, rbc1) / __fmaf_rn(sqrtf(v), rbc2, eps);
+  return __fmaf_rn(wd, p, q);
+}
+
+__global__ __launch_bounds__(256) void lars_norms_kernel(LwSegs sg, const float* __restrict__ p,
+                                                         const float* __restrict__ g,
+                                                         float* __restrict__ partials) {
+  const LwWork w = lw_work(sg);
+  lw_block_sums(lw_sq(lw_load(p, w)), lw_sq(lw_load(g, w)), partials);
+}
+
+__global__ __launch_bounds__(256) void lars_apply_kernel(LwSegs sg, float* __restrict__ p,
+                                                         const float* __restrict__ g,
+                                                         float* __restrict__ v,
+                                                         const float* __restrict__ partials,
+                                                         float lr, const float* __restrict__ lr_ptr,
+                                                         float mu, float eta, float wd) {
+  const LwWork w = lw_work(sg);
+  const float l = lr_ptr ? *lr_ptr : lr;
+  float sp, sgg;
+  lw_segment_sums(partials, w, sp, sgg);
+  const float pn = sqrtf(sp);
+  const float den = __fmaf_rn(wd, pn, sqrtf(sgg));
+  const float r = (pn > 0.f && den > 0.f) ? eta * pn / den : 1.f;
+  if (w.nv == 0) return;
+  float4 pv = lw_load(p, w), vv = lw_load(v, w);
+  const float4 gv = lw_load(g, w);
+  auto upd = [&](float& pp, float gg, float& ac) {  // momentum_kernel's arithmetic on g'
+    const float g1 = r * (gg + wd * pp);
+    ac = mu * ac + g1;
+    pp -= l * ac;
+  };
+  upd(pv.x, gv.x, vv.x);
+  upd(pv.y, gv.y, vv.y);
+  upd(pv.z, gv.z, vv.z);
+  upd(pv.w, gv.w, vv.w);
+  lw_store(p, w, pv);
+  lw_store(v, w, vv);
+}
+
+__global__ __launch_bounds__(256) void lamb_norms_kernel(LwSegs sg, const float* __restrict__ p,
+                                                         const float* __restrict__ g,
+                                                         float* __restrict__ m,
+                                                         float* __restrict__ v,
+                                                         float* __restrict__ partials, float b1,
+                                                         float b2, float omb1, float omb2,
+                                                         float lb1, float lb2, float eps,
+                                                         float wd, int step,
+                                                         const int* __restrict__ step_ptr) {
+  const LwWork w = lw_work(sg);
+  float rbc1, rbc2;
+  lamb_corr(lb1, lb2, step_ptr ? *step_ptr : step, rbc1, rbc2);
+  const float4 pv = lw_load(p, w), gv = lw_load(g, w);
+  float4 mv = lw_load(m, w), vv = lw_load(v, w), u;
+  // omb1 / omb2: 1 - beta rounded ONCE from the host's double (1.f - 0.999f is off by 1.3e-5 of
+  // itself, which a second moment of large gradients shows)
+  auto mom = [&](float pp, float gg, float& mm, float& v2) {
+    mm = b1 * mm + omb1 * gg;
+    v2 = b2 * v2 + omb2 * gg * gg;
+    return lamb_u(pp, mm, v2, rbc1, rbc2, eps, wd);
+  };
+  u.x = mom(pv.x, gv.x, mv.x, vv.x);
+  u.y = mom(pv.y, gv.y, mv.y, vv.y);
+  u.z = mom(pv.z, gv.z, mv.z, vv.z);
+  u.w = mom(pv.w, gv.w, mv.w, vv.w);
+  // (dead lanes add +0 like everything else, also where eps = 0 makes their 0 / 0 a NaN)
+  if (w.nv < 4) u.w = 0.f;
+  if (w.nv < 3) u.z = 0.f;
+  if (w.nv < 2) u.y = 0.f;
+  if (w.nv < 1) u.x = 0.f;
+  lw_store(m, w, mv);
+  lw_store(v, w, vv);
+  lw_block_sums(lw_sq(pv), lw_sq(u), partials);
+}
+
+__global__ __launch_bounds__(256) void lamb_apply_kernel(LwSegs sg, float* __restrict__ p,
+                                                         const float* __restrict__ m,
+                                                         const float* __restrict__ v,
+                                                         const float* __restrict__ partials,
+                                                         float lr, const float* __restrict__ lr_ptr,
+                                                         float lb1, float lb2, float eps,
+                                                         float wd, int step,
+                                                         const int* __restrict__ step_ptr) {
+  const LwWork w = lw_work(sg);
+  const float l = lr_ptr ? *lr_ptr : lr;
+  float rbc1, rbc2;
+  lamb_corr(lb1, lb2, step_ptr ? *step_ptr : step, rbc1, rbc2);
+  float sp, su;
+  lw_segment_sums(partials, w, sp, su);
+  const float pn = sqrtf(sp), un = sqrtf(su);
+  const float lr_r = (pn > 0.f && un > 0.f) ? l * (pn / un) : l;
+  if (w.nv == 0) return;
+  float4 pv = lw_load(p, w);
+  const float4 mv = lw_load(m, w), vv = lw_load(v, w);
+  pv.x -= lr_r * lamb_u(pv.x, mv.x, vv.x, rbc1, rbc2, eps, wd);
+  pv.y -= lr_r * lamb_u(pv.y, mv.y, vv.y, rbc1, rbc2, eps, wd);
+  pv.z -= lr_r * lamb_u(pv.z, mv.z, vv.z, rbc1, rbc2, eps, wd);
+  pv.w -= lr_r * lamb_u(pv.w, mv.w, vv.w, rbc1, rbc2, eps, wd);
+  lw_store(p, w, pv);
+}
+
+// The segment table of a flat buffer of n elements cut at offsets[0..nseg] (offsets[0] = 0,
+// offsets[nseg] = n): throws unless there are 1..8 non-empty segments, every start a multiple of
+// 4 elements (only the buffer's end may be ragged) and the buffers are 16-byte aligned.
+LwSegs layerwise_segments(const long long* offsets, int nseg) {
+  if (nseg < 1 || nseg > kLwMaxSegments)
+    throw std::runtime_error("layerwise: 1.." + std::to_string(kLwMaxSegments) +
+                             " segments, got " + std::to_string(nseg));
+  if (offsets[0] != 0) throw std::runtime_error("layerwise: the first segment starts at 0");
+  LwSegs sg = {};
+  sg.nseg = nseg;
+  long long blocks = 0;
+  for (int k = 0; k < nseg; ++k) {
+    const long long a = offsets[k], b = offsets[k + 1];
+    if (b <= a) throw std::runtime_error("layerwise: segment offsets must increase");
+    if (a & 3)
+      throw std::runtime_error("layerwise: every segment must start at a multiple of 4 elements "
+                               "(got " + std::to_string(a) + ")");
+    if (b > 0x7fffffffLL - kLwBlock || blocks + (b - a + kLwBlock - 1) / kLwBlock > 0x3fffffffLL)
+      throw std::runtime_error("layerwise: buffer too large");
+    sg.off[k] = (int)a;
+    sg.blk[k] = (int)blocks;
+    blocks += (b - a + kLwBlock - 1) / kLwBlock;
+  }
+  for (int k = nseg; k <= kLwMaxSegments; ++k) {  // (unused entries: the end, so any scan is safe)
+    sg.off[k] = (int)offsets[nseg];
+    sg.blk[k] = (int)blocks;
+  }
+  return sg;
+}
+
+int layerwise_blocks(const LwSegs& sg) { return sg.blk[sg.nseg]; }
+
+void lars_launch(const LwSegs& sg, float* p, const float* g, float* v, float* partials, float lr,
+                 const float* lr_ptr, float mu, float eta, float wd, hipStream_t s) {
+  if (!p || !g || !v || !partials) throw std::runtime_error("lars: null buffer");
+  check_align(p, "lars");
+  check_align(g, "lars");
+  check_align(v, "lars");
+  if (reinterpret_cast<uintptr_t>(partials) & 7)
+    throw std::runtime_error("lars: partials must be 8-byte aligned");
+  const dim3 grid((unsigned)layerwise_blocks(sg));
+  hipLaunchKernelGGL(lars_norms_kernel, grid, dim3(256), 0, s, sg, p, g, partials);
+  hipLaunchKernelGGL(lars_apply_kernel, grid, dim3(256), 0, s, sg, p, g, v, partials, lr, lr_ptr,
+                     mu, eta, wd);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+void lamb_launch(const LwSegs& sg, float* p, const float* g, float* m, float* v, float* partials,
+                 float lr, const float* lr_ptr, double beta1, double beta2, float eps, float wd,
+                 int step, const int* step_ptr, hipStream_t s) {
+  if (!p || !g || !m || !v || !partials) throw std::runtime_error("lamb: null buffer");
+  if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0))
+    throw std::runtime_error("lamb: beta1 and beta2 must lie in [0, 1)");
+  const float b1 = (float)beta1, b2 = (float)beta2;
+  const float lb1 = (float)std::log(beta1), lb2 = (float)std::log(beta2);  // (-inf at 0: bc = 1)
+  check_align(p, "lamb");
+  check_align(g, "lamb");
+  check_align(m, "lamb");
+  check_align(v, "lamb");
+  if (reinterpret_cast<uintptr_t>(partials) & 7)
+    throw std::runtime_error("lamb: partials must be 8-byte aligned");
+  const dim3 grid((unsigned)layerwise_blocks(sg));
+  hipLaunchKernelGGL(lamb_norms_kernel, grid, dim3(256), 0, s, sg, p, g, m, v, partials, b1, b2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), lb1, lb2, eps, wd, step,
+                     step_ptr);
+  hipLaunchKernelGGL(lamb_apply_kernel, grid, dim3(256), 0, s, sg, p, m, v, partials, lr, lr_ptr,
+                     lb1, lb2, eps, wd, step, step_ptr);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

@@ -211,8 +211,16 @@ def define_reference_flags(flag_values=FLAGS):
                   "checkpoints carry them; not with --use_locking.  mirrored, --model mlp: "
                   "applied inside the fused two-launch step (one GPU), by the all-reduce engine "
                   "(several) or the autograd path (--device cpu); slots in the checkpoints; "
-                  "not with --zero1", fv)
-    DEFINE_float("momentum", 0.9, "--optimizer momentum: the momentum", fv)
+                  "not with --zero1.  lars | lamb (layer-wise adaptive rates for large batches, "
+                  "ops/layerwise.py): --strategy mirrored --model mlp only, every tensor's step "
+                  "scaled by a trust ratio of norms computed by two HIP launches after the "
+                  "gradient; lars is momentum SGD (--momentum, --lars_eta), lamb is Adam "
+                  "(--adam_*); --weight_decay is part of both rules; not with --nesterov, "
+                  "--noadamw, --zero1, ps_async or --model bert|resnet50", fv)
+    DEFINE_float("lars_eta", 0.001,
+                 "--optimizer lars: the trust coefficient eta (finite, > 0) of r = eta |p| / "
+                 "(|g| + weight_decay |p|)", fv)
+    DEFINE_float("momentum", 0.9, "--optimizer momentum | lars: the momentum", fv)
     DEFINE_float("adam_beta1", 0.9, "--optimizer adam: beta1", fv)
     DEFINE_float("adam_beta2", 0.999, "--optimizer adam: beta2", fv)
     DEFINE_float("adam_epsilon", 1e-8, "--optimizer adam: epsilon", fv)

@@ -245,7 +245,9 @@ class PipelinedOpt:
         self.ema = ema
         self.shadow = (torch.zeros(NPARAM, device=device, dtype=torch.float32)
                        if ema is not None else None)
-        if kind not in self.KINDS and not (
+        # (lars / lamb, ops/layerwise.py: the gradient-buffer engine keeps its slot planes, step
+        # pair, schedule block and shadow here; no two-launch instantiation applies them)
+        if kind not in self.KINDS and kind not in ("lars", "lamb") and not (
                 kind == "sgd" and (schedule is not None or decay is not None
                                    or ema is not None)):
             raise ValueError("the fused step's optimizers are momentum and adam, got %r" % (kind,))

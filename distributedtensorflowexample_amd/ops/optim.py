@@ -64,6 +64,85 @@ def adam_(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0
     return p
 
 
+def _layerwise_args(name, p, segments, partials, *planes, lr_tensor=None):
+    """The GPU checks both layer-wise functions share -> (segment table, partials)."""
+    from . import layerwise
+
+    seg = layerwise.check_segments(segments, p.numel())
+    check_gpu_f32(p, *planes, lr_tensor)
+    for t in (p,) + planes:
+        if t.numel() != p.numel():
+            raise ValueError("%s: every plane must have p's %d elements" % (name, p.numel()))
+        if t.data_ptr() % 16:
+            raise ValueError("%s: buffers must be 16-byte aligned" % name)
+    nb = layerwise.num_blocks(seg)
+    if partials is None:  # (a caller that captures a graph or steps in a loop brings its own)
+        partials = torch.empty(2 * nb, device=p.device, dtype=torch.float32)
+    check_gpu_f32(partials)
+    if partials.numel() < 2 * nb or partials.data_ptr() % 8:
+        raise ValueError("%s: partials must hold 2 floats for each of the %d workgroups, 8-byte "
+                         "aligned (got %d floats)" % (name, nb, partials.numel()))
+    return seg, partials
+
+
+def _segment_ratio(num, den, scale=1.0):
+    """``scale * num / den`` where both are > 0, else 1 (the trust-ratio fallback), in f32."""
+    return scale * num / den if (float(num) > 0.0 and float(den) > 0.0) else num.new_tensor(1.0)
+
+
+def lars_(p, g, buf, lr, segments, momentum=0.9, eta=0.001, weight_decay=0.0, lr_tensor=None,
+          partials=None):
+    """LARS (``ops/layerwise.py``): per segment ``r = eta |p| / (|g| + wd |p|)``, then
+    ``momentum_``'s arithmetic on ``g' = r (g + wd p)``.  ``segments``: the boundaries
+    ``(0, ..., n)``, at most 8 segments, each start a multiple of 4.  GPU: two launches;
+    ``partials`` (f32, ``2 * layerwise.num_blocks(segments)``) is scratch for the norms."""
+    if not p.is_cuda:
+        from . import layerwise
+
+        seg = layerwise.check_segments(segments, p.numel())
+        with torch.no_grad():
+            l = float(lr if lr_tensor is None else lr_tensor.item())
+            for a, b in zip(seg, seg[1:]):
+                pn, gn = p[a:b].norm(), g[a:b].norm()
+                r = _segment_ratio(pn, gn + weight_decay * pn, float(eta))
+                buf[a:b].mul_(momentum).add_(r * (g[a:b] + weight_decay * p[a:b]))
+                p[a:b].add_(buf[a:b], alpha=-l)
+        return p
+    seg, partials = _layerwise_args("lars_", p, segments, partials, g, buf, lr_tensor=lr_tensor)
+    hip().lars(seg, ptr(p), ptr(g), ptr(buf), ptr(partials), float(lr), ptr(lr_tensor),
+               float(momentum), float(eta), float(weight_decay), stream_handle())
+    return p
+
+
+def lamb_(p, g, m, v, lr, step, segments, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+          step_tensor=None, lr_tensor=None, partials=None):
+    """LAMB (``ops/layerwise.py``): Adam's bias-corrected direction plus ``wd p`` is ``u``; per
+    segment ``r = |p| / |u|``; ``p -= lr r u``.  ``step`` is 1-based, as ``adam_``'s; ``segments``
+    and ``partials`` as ``lars_``'s."""
+    if not p.is_cuda:
+        from . import layerwise
+
+        seg = layerwise.check_segments(segments, p.numel())
+        with torch.no_grad():
+            l = float(lr if lr_tensor is None else lr_tensor.item())
+            t = int(step if step_tensor is None else step_tensor.item())
+            m.mul_(beta1).add_(g, alpha=1 - beta1)
+            v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            u = (m / (1 - beta1 ** t)) / (v.sqrt() / ((1 - beta2 ** t) ** 0.5) + eps)
+            u.add_(p, alpha=weight_decay)
+            for a, b in zip(seg, seg[1:]):
+                r = _segment_ratio(p[a:b].norm(), u[a:b].norm())
+                p[a:b].sub_(u[a:b] * (l * r))
+        return p
+    seg, partials = _layerwise_args("lamb_", p, segments, partials, g, m, v, lr_tensor=lr_tensor)
+    if step_tensor is not None and step_tensor.dtype != torch.int32:
+        raise TypeError("step_tensor must be int32")
+    hip().lamb(seg, ptr(p), ptr(g), ptr(m), ptr(v), ptr(partials), float(lr), ptr(lr_tensor),
+               float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+               ptr(step_tensor), stream_handle())
+    return p
+
+
 def ema_(shadow, p, decay, num_updates=False, step=0, step_tensor=None):
     """Moving average of the parameters (``ops/ema.py``), in place on ``shadow``:
     ``shadow -= (1 - d_t) * (shadow - p)`` with ``d_t = decay`` or, with ``num_updates``,

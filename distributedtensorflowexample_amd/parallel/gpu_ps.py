@@ -98,7 +98,7 @@ class GpuPSStore:
             raise ValueError("gpu_ps: sync_replicas must be >= 0")
         self._rounds = None
         # the optimizer's slot planes: [[TF names of plane k]], and the kernels' hyper words
-        self.optimizer = gpu_ps_optim.check_kind(optimizer)
+        self.optimizer = gpu_ps_optim.check_store_kind(optimizer)
         self.slot_names = gpu_ps_optim.slot_names(self.optimizer, VAR_NAMES)
         self._hyper = gpu_ps_optim.hyper_args(self.optimizer, momentum, beta1, beta2, epsilon)
         nbytes = hip().GpuParamStore.handle_size()

@@ -20,11 +20,16 @@ from __future__ import annotations
 
 import numpy as np
 
-KINDS = ("sgd", "momentum", "adam")
+# lars / lamb (ops/layerwise.py): the fused MLP trainer's gradient-buffer engine only -- the
+# stores have no norm pass (STORE_KINDS are theirs); named here so --optimizer has one list and
+# the savers' slot mechanism checkpoints their planes
+KINDS = ("sgd", "momentum", "adam", "lars", "lamb")
+STORE_KINDS = KINDS[:3]
 # TF's slot names (tf.train.MomentumOptimizer / AdamOptimizer): <variable>/<slot>, in the
 # order of the store's planes
-SLOT_NAMES = {"sgd": (), "momentum": ("Momentum",), "adam": ("Adam", "Adam_1")}
-DEFAULTS = {"momentum": 0.9, "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8}
+SLOT_NAMES = {"sgd": (), "momentum": ("Momentum",), "adam": ("Adam", "Adam_1"),
+              "lars": ("Momentum",), "lamb": ("m", "v")}
+DEFAULTS = {"momentum": 0.9, "beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8, "lars_eta": 0.001}
 
 
 def check_kind(kind):
@@ -34,8 +39,17 @@ def check_kind(kind):
     return kind
 
 
+def check_store_kind(kind):
+    """``check_kind`` for the parameter stores, whose apply kernels have no norm pass."""
+    kind = check_kind(kind)
+    if kind not in STORE_KINDS:
+        raise ValueError("--optimizer %s is the fused MLP trainer's (--strategy mirrored --model "
+                         "mlp): the parameter stores have no norm pass" % kind)
+    return kind
+
+
 def num_slots(kind):
-    """Planes the store appends for ``kind`` (also the kind's number in the control block)."""
+    """Planes the store appends for ``kind`` (also a store kind's number in the control block)."""
     return len(SLOT_NAMES[check_kind(kind)])
 
 
@@ -45,21 +59,24 @@ def slot_names(kind, var_names):
 
 
 def hyper_args(kind, momentum=DEFAULTS["momentum"], beta1=DEFAULTS["beta1"],
-               beta2=DEFAULTS["beta2"], epsilon=DEFAULTS["epsilon"]):
+               beta2=DEFAULTS["beta2"], epsilon=DEFAULTS["epsilon"],
+               lars_eta=DEFAULTS["lars_eta"]):
     """The kernels' three hyper-parameter words ``(h0, h1, h2)``: momentum ``(mu, 0, 0)``,
-    adam ``(beta1, beta2, epsilon)``, sgd none."""
+    adam and lamb ``(beta1, beta2, epsilon)``, lars ``(mu, eta, 0)``, sgd none."""
     kind = check_kind(kind)
     if kind == "momentum":
         return (float(momentum), 0.0, 0.0)
-    if kind == "adam":
+    if kind in ("adam", "lamb"):
         return (float(beta1), float(beta2), float(epsilon))
+    if kind == "lars":
+        return (float(momentum), float(lars_eta), 0.0)
     return ()
 
 
 def validate(kind, ps_device, use_locking):
     """The combinations ``--optimizer`` supports; ValueError otherwise (before any device or
     server is touched)."""
-    kind = check_kind(kind)
+    kind = check_store_kind(kind)
     if kind == "sgd":
         return kind
     if str(ps_device) != "gpu":
@@ -105,7 +122,7 @@ def apply_reference(kind, p, g, slots, lr, t, hyper, fma=False):
     sync round :func:`mean_gradient` of the tickets' gradients.  ``fma=True`` fuses every
     ``a * b + c`` of the update (see ``gpu_ps_sync.round_reference``); for data on which every
     product and sum is exact both give the same bits."""
-    kind = check_kind(kind)
+    kind = check_store_kind(kind)
     p = np.asarray(p, dtype=np.float32)
     g = np.asarray(g, dtype=np.float32)
     slots = [np.asarray(s, dtype=np.float32) for s in slots]

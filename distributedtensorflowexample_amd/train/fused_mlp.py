@@ -152,6 +152,21 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   outside the step and the graphs); ``batch()`` returns its rows.  Everything the large-batch
   engine supports works unchanged.  ``batch_size <= 256`` is latency-bound and gains nothing:
   refused in the constructor.  ``compute_dtype="fp32"`` launches exactly today's kernels.
+* ``optimizer="lars" | "lamb"`` (``--optimizer``, ``lars_eta``; ``ops/layerwise.py`` has the
+  definition): layer-wise adaptive rates for large batches.  The update of every tensor (a
+  *segment* of the flat buffer: W1t, b1, W2t, b2, from ``mlp_model.h``) is scaled by a trust ratio
+  of Euclidean norms, so the rule needs a reduction over each tensor between forming the update
+  and applying it -- and a gradient to take the norm of, which the two-launch step never holds.
+  The trainer therefore IS the gradient-buffer engine at every batch size, one GPU included
+  (``pipelined``, ``direct`` and ``host_loop_ok`` are false): ``mlp_step.step_grad`` up to 256
+  rows, the large-batch launches above, then ``ops.optim.lars_`` / ``lamb_`` in place -- two
+  launches over a segment-aligned grid (``csrc/kernels/optim.hip``), no atomics, no host
+  read-back, bit-reproducible and captured in ``run()``'s graphs; the rate and LAMB's ``t`` come
+  from the device.  ``weight_decay`` is the rule's own term; ``nesterov`` and ``adamw=False`` are
+  refused.  The trainer owns the partial-sum scratch, the slot planes (lars ``[accum]``, lamb
+  ``[m, v]``) and the segment table.  Schedules, the moving average, activations, shuffle, the
+  ``allreduce`` hook, ``compute_dtype="bf16"`` and (up to 256 rows) dropout compose unchanged;
+  the exchange engines, ``pipeline=False`` and the persistent launch refuse them.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -168,6 +183,7 @@ import torch
 from ..ops import dropout as dropout_mod
 from ..ops import ema as ema_mod
 from ..ops import hidden_act
+from ..ops import layerwise as layerwise_mod
 from ..ops import lr_schedule as lr_schedule_mod
 from ..ops import mlp_large_batch, mlp_step, optim
 from ..ops import weight_decay as weight_decay_mod
@@ -182,7 +198,7 @@ class FusedMLPTrainer:
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
                  beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0,
                  weight_decay=0.0, adamw=True, nesterov=False, activation="sigmoid",
-                 ema_decay=0.0, ema_num_updates=False, compute_dtype="fp32"):
+                 ema_decay=0.0, ema_num_updates=False, compute_dtype="fp32", lars_eta=0.001):
         # --ema_decay: refused first where no launch carries a shadow plane
         self.avg = ema_mod.resolve(ema_decay, ema_num_updates)
         if self.avg is not None:
@@ -215,6 +231,13 @@ class FusedMLPTrainer:
         # --weight_decay / --nesterov: refused first where the update has no such term
         self.decay = weight_decay_mod.resolve(gpu_ps_optim.check_kind(optimizer), weight_decay,
                                               adamw, nesterov, momentum)
+        # --optimizer lars | lamb: the decay is a term of the layer-wise rule itself (validated
+        # with it; Nesterov and adamw=False are refused), not one of the first launch's words
+        self.lw = layerwise_mod.resolve(optimizer, weight_decay, lars_eta, momentum=momentum,
+                                        beta1=beta1, beta2=beta2, epsilon=epsilon,
+                                        nesterov=nesterov, adamw=adamw)
+        if self.lw is not None:
+            self.decay = None
         if self.decay is not None:
             if fused_comm is not None or factor_comm is not None:
                 raise ValueError("weight_decay / nesterov: the exchange engines (fused_comm / "
@@ -337,7 +360,10 @@ class FusedMLPTrainer:
         # single GPU without a communicator, the fused engine or the factor engine (batch
         # <= 128): the two-launch pipelined step
         # (batch_size > 256: the large-batch engine is neither pipelined nor direct)
-        self.pipelined = bool(pipeline and not self.large and allreduce is None and (
+        # (lars / lamb: a layer-wise rule takes norms of the gradient, and the two-launch step
+        # never holds one -- the gradient-buffer engine at every batch size)
+        self.pipelined = bool(pipeline and not self.large and self.lw is None
+                              and allreduce is None and (
             (self.world_size == 1 and factor_comm is None and fused_comm is None)
             or fused_comm is not None
             or (factor_comm is not None and self.B <= 128)))
@@ -354,6 +380,11 @@ class FusedMLPTrainer:
             self.opt.set_step(global_step)
             if self.avg is not None:
                 self.opt.shadow.copy_(self.bufs[0])  # shadow_0: the initial parameters, as in TF
+        # lars / lamb: the segment table (the MLP's four tensors) and the norm launches' scratch
+        if self.lw is not None:
+            self.segments = layerwise_mod.mlp_segments()
+            self._partials = torch.zeros(2 * layerwise_mod.num_blocks(self.segments),
+                                         device=self.device, dtype=torch.float32)
         # the all-reduce engine's scheduled rate (ops.optim's lr_tensor)
         self._lr_dev = (torch.zeros(1, device=self.device, dtype=torch.float32)
                         if self.sched is not None else None)
@@ -387,7 +418,7 @@ class FusedMLPTrainer:
     @property
     def direct(self):
         """SGD apply fused into the backward kernel (one GPU, or the fused xGMI exchange)."""
-        return not self.pipelined and not self.large and (
+        return not self.pipelined and not self.large and self.lw is None and (
             self.fused_comm is not None or self.factor_comm is not None
             or (self.allreduce is None and self.world_size == 1))
 
@@ -463,6 +494,13 @@ class FusedMLPTrainer:
         elif self.optimizer == "momentum":
             optim.momentum_(p, self.grad, slots[0], self.lr, momentum=h[0], lr_tensor=lrt,
                             **(d.momentum_kw if d else {}))
+        elif self.optimizer == "lars":
+            optim.lars_(p, self.grad, slots[0], self.lr, self.segments, lr_tensor=lrt,
+                        partials=self._partials, **self.lw.kw)
+        elif self.optimizer == "lamb":
+            optim.lamb_(p, self.grad, slots[0], slots[1], self.lr, 0, self.segments,
+                        step_tensor=self.ws.ctr, lr_tensor=lrt, partials=self._partials,
+                        **self.lw.kw)
         else:
             kw = d.adam_kw if d else dict(weight_decay=0.0, adamw=False)
             optim.adam_(p, self.grad, slots[0], slots[1], self.lr, 0, beta1=h[0], beta2=h[1],
@@ -917,6 +955,10 @@ class FusedMLPTrainer:
             raise ValueError("run_persistent: the persistent launch keeps no moving average of "
                              "the parameters (ema_decay is not supported); use run() / "
                              "run_launched()")
+        if self.lw is not None:
+            raise ValueError("run_persistent: the persistent launch applies gradient descent "
+                             "only (optimizer %s needs the gradient-buffer engine); use run()"
+                             % self.optimizer)
         if not self.persistent_ok:
             raise RuntimeError("run_persistent: single-GPU step with batch <= 128 only "
                                "(shuffle off, optimizer sgd)")

@@ -22,6 +22,7 @@ import torch.distributed as dist
 from ..models import mlp as mlp_model
 from ..ops import dropout as dropout_mod
 from ..ops import ema as ema_mod
+from ..ops import layerwise as layerwise_mod
 from ..ops import hidden_act
 from ..ops import lr_schedule, mlp_step, nn, optim
 from ..ops import weight_decay as weight_decay_mod
@@ -67,6 +68,12 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                   beta1=float(getattr(flags, "adam_beta1", gpu_ps_optim.DEFAULTS["beta1"])),
                   beta2=float(getattr(flags, "adam_beta2", gpu_ps_optim.DEFAULTS["beta2"])),
                   epsilon=float(getattr(flags, "adam_epsilon", gpu_ps_optim.DEFAULTS["epsilon"])))
+    # --optimizer lars | lamb (ops/layerwise.py): the fused trainer's gradient-buffer engine on the
+    # GPU, ops.optim's CPU branches on the autograd path; slots as <variable>/Momentum, /m, /v
+    lw = layerwise_mod.from_flags(flags)
+    if lw is not None and getattr(flags, "zero1", False):
+        layerwise_mod.refuse(flags, "--zero1 (a sharded owner sees a slice of a tensor, not its "
+                                    "norm)")
     if opt_kind != "sgd" and getattr(flags, "zero1", False):
         raise ValueError("--optimizer %s does not support --zero1: the sharded update applies "
                          "gradient descent only" % opt_kind)
@@ -200,7 +207,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              nesterov=decay.nesterov if decay else False, activation=act,
                              ema_decay=avg.decay if avg else 0.0,
                              ema_num_updates=avg.num_updates if avg else False,
-                             compute_dtype="bf16" if dtype == "bf16" else "fp32", **opt_kw)
+                             compute_dtype="bf16" if dtype == "bf16" else "fp32",
+                             lars_eta=lw.eta if lw else layerwise_mod.DEFAULT_ETA, **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -222,6 +230,7 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         cpu_slots = [torch.zeros(mlp_step.NPARAM)
                      for _ in range(gpu_ps_optim.num_slots(opt_kind))]
         cpu_shadow = model.flat.detach().clone() if avg is not None else None  # shadow_0 = p_0
+        cpu_segments = layerwise_mod.mlp_segments() if lw is not None else None
         get_state = lambda: (get_params(), [t.clone() for t in cpu_slots],  # noqa: E731
                              None if cpu_shadow is None else cpu_shadow.clone())
 
@@ -271,6 +280,11 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                                 beta2=opt_kw["beta2"], eps=opt_kw["epsilon"],
                                 **(decay.adam_kw if decay
                                    else dict(weight_decay=0.0, adamw=False)))
+                elif opt_kind == "lars":
+                    optim.lars_(model.flat.data, g, cpu_slots[0], lr, cpu_segments, **lw.kw)
+                elif opt_kind == "lamb":  # t as adam's
+                    optim.lamb_(model.flat.data, g, cpu_slots[0], cpu_slots[1], lr, i + 1,
+                                cpu_segments, **lw.kw)
                 else:
                     optim.sgd_(model.flat.data, g, lr, **(decay.sgd_kw if decay else {}))
                 if avg is not None:  # after the update; t = global_step + 1 of this step

@@ -73,6 +73,20 @@ def main(argv=None):
         from distributedtensorflowexample_amd.train.eval_job import eval_job
 
         return eval_job(FLAGS)
+    # --optimizer lars | lamb / --lars_eta: the mirrored MLP's update only (ops/layerwise.py)
+    from distributedtensorflowexample_amd.ops import layerwise
+
+    try:
+        if FLAGS.strategy != "mirrored":
+            layerwise.refuse(FLAGS, "--strategy ps_async (--ps_device cpu and gpu)")
+        elif FLAGS.model != "mlp":
+            layerwise.refuse(FLAGS, "--model %s" % FLAGS.model)
+        elif getattr(FLAGS, "zero1", False):
+            layerwise.refuse(FLAGS, "--zero1 (a sharded owner sees a slice of a tensor, not its "
+                                    "norm)")
+        layerwise.from_flags(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if FLAGS.strategy == "mirrored" and FLAGS.optimizer != "sgd":
         # --optimizer momentum | adam: the fused MLP trainer's and the GPU parameter store's
         # (train/worker.py validates the ps_async combinations); never silently ignored

@@ -113,7 +113,7 @@ def part_optim(a):
     s = stream_handle(dev)
     g = torch.randn(n, device=dev) * 1e-3
     stores, blocks = [], {}
-    for kind in gpu_ps_optim.KINDS:
+    for kind in gpu_ps_optim.STORE_KINDS:
         k, hyper = gpu_ps_optim.num_slots(kind), gpu_ps_optim.hyper_args(kind)
         async_st = hip().GpuParamStore(0, n, True, 0, k)
         sync_st = hip().GpuParamStore(0, n, True, 1, k)
