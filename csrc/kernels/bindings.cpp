@@ -494,6 +494,18 @@ PYBIND11_MODULE(_hip, m) {
                       P<const int>(step_ptr), S(s));
   }, "LAMB in place: m, v and per-segment norms of p and u into partials, then p -= lr r_k u "
      "(t = *step_ptr or step)");
+  // Clipping by the global norm (ops/clip.py): partials holds gnorm_blocks(n) floats
+  m.def("gnorm_blocks", &dtfx::gnorm_blocks,
+        "workgroups of 1,024 elements = partial sums of a buffer of n floats");
+  m.def("gnorm_partials", [](long long n, uintptr_t g, uintptr_t partials, uintptr_t s) {
+    dtfx::gnorm_partials_launch(n, P<const float>(g), P<float>(partials), S(s));
+  }, "partials[block] = sum of squares of the block's 1,024 elements of g (fixed order)");
+  m.def("clip_scale", [](long long n, uintptr_t g, uintptr_t partials, int nblk, float clip,
+                         float pre, uintptr_t gnorm, uintptr_t s) {
+    dtfx::clip_scale_launch(n, P<float>(g), P<const float>(partials), nblk, clip, pre,
+                            P<float>(gnorm), S(s));
+  }, "g *= pre * clip / max(norm, clip) in place, norm = pre * sqrt(sum of the partials); gnorm "
+     "(optional, 0): one float that receives norm");
   m.def("scale", [](long long n, uintptr_t x, float a, uintptr_t s) {
     dtfx::scale_launch(n, P<float>(x), a, S(s));
   });
@@ -554,10 +566,16 @@ PYBIND11_MODULE(_hip, m) {
     dtfx::mlp_lb_wgrad_launch(P<const float>(x), P<float>(ws), B, S(s));
   }, "factors -> one partial gradient plane per batch slice");
   m.def("mlp_lb_reduce", [](uintptr_t ws, uintptr_t grad, uintptr_t ctr, uintptr_t stats, int ring,
-                            int B, uintptr_t s) {
+                            int B, uintptr_t s, uintptr_t partials) {
     dtfx::mlp_lb_reduce_launch(P<const float>(ws), P<float>(grad), P<int>(ctr), P<float>(stats),
-                               ring, B, S(s));
-  }, "planes -> flat gradient [79510] (slice order), stats[global_step % ring], global_step += 1");
+                               ring, B, S(s), P<float>(partials));
+  }, py::arg("ws"), py::arg("grad"), py::arg("ctr"), py::arg("stats"), py::arg("ring"),
+     py::arg("B"), py::arg("stream"), py::arg("partials") = 0,
+     "planes -> flat gradient [79510] (slice order), stats[global_step % ring], global_step += 1; "
+     "partials (mlp_lb_reduce_partials(B) floats): also each workgroup's sum of squares of the "
+     "gradient words it stored, as gnorm_partials leaves them");
+  m.def("mlp_lb_reduce_partials", &dtfx::mlp_lb_reduce_partials,
+        "workgroups of the reduce launch for batch B = partial sums its `partials` must hold");
   // Its mixed-precision form (csrc/kernels/mlp_large_batch_bf16.hip): xh is the bf16 dataset
   m.def("mlp_lbh_workspace_floats", &dtfx::mlp_lbh_workspace_floats,
         "floats of the bf16 large-batch workspace for batch B (last 4 words: the hand-off words)");
@@ -580,10 +598,12 @@ PYBIND11_MODULE(_hip, m) {
     dtfx::mlp_lbh_wgrad_launch(P<const unsigned short>(xh), P<float>(ws), B, S(s));
   }, "bf16 factors -> one partial gradient plane per batch slice");
   m.def("mlp_lbh_reduce", [](uintptr_t ws, uintptr_t grad, uintptr_t ctr, uintptr_t stats,
-                             int ring, int B, uintptr_t s) {
+                             int ring, int B, uintptr_t s, uintptr_t partials) {
     dtfx::mlp_lbh_reduce_launch(P<const float>(ws), P<float>(grad), P<int>(ctr), P<float>(stats),
-                                ring, B, S(s));
-  }, "mlp_lb_reduce on the bf16 workspace's planes");
+                                ring, B, S(s), P<float>(partials));
+  }, py::arg("ws"), py::arg("grad"), py::arg("ctr"), py::arg("stats"), py::arg("ring"),
+     py::arg("B"), py::arg("stream"), py::arg("partials") = 0,
+     "mlp_lb_reduce on the bf16 workspace's planes");
   m.def("calib", [](int mode, int grid, int block, uintptr_t ctr, uintptr_t data, uintptr_t out,
                     uintptr_t s) {
     dtfx::calib_launch(mode, grid, block, P<const int>(ctr), P<const float>(data), P<float>(out),

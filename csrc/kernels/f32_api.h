@@ -52,6 +52,15 @@ void lars_launch(const LwSegs& sg, float* p, const float* g, float* v, float* pa
 void lamb_launch(const LwSegs& sg, float* p, const float* g, float* m, float* v, float* partials,
                  float lr, const float* lr_ptr, double beta1, double beta2, float eps, float wd,
                  int step, const int* step_ptr, hipStream_t s);
+// Clipping by the global norm (ops/clip.py).  gnorm_blocks(n): the workgroups of 1,024 elements
+// = partial sums of a buffer of n floats (throws outside 1 .. 2^31 - 1025).  gnorm_partials
+// rewrites partials[0 .. nblk) with the sums of squares of g (16-byte aligned); clip_scale re-adds
+// them, multiplies g in place by pre * clip / max(pre * sqrt(sum), clip) and, with gnorm_out
+// non-null, stores pre * sqrt(sum) there.
+int gnorm_blocks(long long n);
+void gnorm_partials_launch(long long n, const float* g, float* partials, hipStream_t s);
+void clip_scale_launch(long long n, float* g, const float* partials, int nblk, float clip,
+                       float pre, float* gnorm_out, hipStream_t s);
 void scale_launch(long long n, float* x, float a, hipStream_t s);
 void counter_add_launch(int* c, int d, hipStream_t s);
 void philox_init_launch(long long n, float* out, unsigned long long seed, unsigned long long offset,

@@ -55,7 +55,10 @@
 //     gradient words and writes mean loss and accuracy to stats[global_step % stats_ring], then
 //     advances global_step: mlp_wgrad's contract (mlp_step_3launch.h), one thread, no other
 //     launch touches the counter.  Folding this launch into the optimizer kernels is left open.
+//     With a `partials` buffer (global-norm clipping) the CLIP instantiation also leaves each
+//     workgroup's sum of squares of the gradient words it stored.
 #include "common.h"
+#include "gnorm.h"
 #include "mlp_model.h"
 #include "mlp_step_api.h"
 
@@ -444,13 +447,13 @@ __global__ __launch_bounds__(NW * 64) void mlp_lb_wgrad_kernel(const float* __re
 // ---------------------------------------------------------------------------
 // (c) planes -> gradient, stats record, global_step
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mlp_lb_reduce_kernel(const float* __restrict__ planes,
-                                                            int S, float* __restrict__ grad,
-                                                            int* __restrict__ ctr,
-                                                            float* __restrict__ stats,
-                                                            int stats_ring, int B) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= NV4) return;
+// Thread i's float4 of the gradient (i < NV4).  CLIP: returns the sum of squares of the gradient
+// words it stored, in element order -- the loss and correct sums behind b2 are no gradient words.
+template <bool CLIP>
+__device__ __forceinline__ float lb_reduce_item(int i, const float* __restrict__ planes, int S,
+                                                float* __restrict__ grad, int* __restrict__ ctr,
+                                                float* __restrict__ stats, int stats_ring,
+                                                int B) {
   const float* src = planes + (size_t)i * 4;
   float4 v = f4(src);
 #pragma unroll 4
@@ -463,7 +466,7 @@ __global__ __launch_bounds__(256) void mlp_lb_reduce_kernel(const float* __restr
   }
   if (i < NV4 - 1) {
     *reinterpret_cast<float4*>(grad + (size_t)i * 4) = v;
-    return;
+    return CLIP ? lw_sq(v) : 0.f;
   }
   grad[NPARAM - 2] = v.x;
   grad[NPARAM - 1] = v.y;
@@ -474,6 +477,29 @@ __global__ __launch_bounds__(256) void mlp_lb_reduce_kernel(const float* __restr
     st[1] = v.w / (float)B;
   }
   *ctr = step + 1;
+  return CLIP ? lw_sq(make_float4(v.x, v.y, 0.f, 0.f)) : 0.f;
+}
+
+// CLIP (global-norm clipping, ops/clip.py): every workgroup also writes the sum of squares of the
+// 1,024 gradient words it stored to partials[block] -- optim.hip's gnorm_partials geometry and
+// order (gnorm.h), taken from the registers that hold the sums, so the norm costs no second pass
+// over the gradient.  Threads past the last float4 add +0 and stay for the barrier.
+template <bool CLIP>
+__global__ __launch_bounds__(256) void mlp_lb_reduce_kernel(const float* __restrict__ planes,
+                                                            int S, float* __restrict__ grad,
+                                                            int* __restrict__ ctr,
+                                                            float* __restrict__ stats,
+                                                            int stats_ring, int B,
+                                                            float* __restrict__ partials) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if constexpr (!CLIP) {
+    if (i >= NV4) return;
+    lb_reduce_item<false>(i, planes, S, grad, ctr, stats, stats_ring, B);
+  } else {
+    const float sq =
+        i < NV4 ? lb_reduce_item<true>(i, planes, S, grad, ctr, stats, stats_ring, B) : 0.f;
+    gn_block_sum(sq, partials);
+  }
 }
 
 static void check_batch(const char* who, int B) {
@@ -523,22 +549,33 @@ void mlp_lb_wgrad_launch(const float* x, float* ws, int B, hipStream_t stream) {
   DTFX_HIP_CHECK(hipGetLastError());
 }
 
+int mlp_lb_reduce_partials(int B) {
+  mlplb::check_batch("mlp_lb_reduce_partials", B);
+  return (mlplb::NV4 + 255) / 256;
+}
+
 void mlp_lb_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
-                          int B, hipStream_t stream) {
+                          int B, hipStream_t stream, float* partials) {
   using namespace mlplb;
   check_batch("mlp_lb_reduce", B);
   const LbLayout L = lb_layout(B);
-  mlp_lb_reduce_planes_launch(ws + L.planes, L.S, grad, ctr, stats, stats_ring, B, stream);
+  mlp_lb_reduce_planes_launch(ws + L.planes, L.S, grad, ctr, stats, stats_ring, B, stream,
+                              partials);
 }
 
 void mlp_lb_reduce_planes_launch(const float* planes, int S, float* grad, int* ctr, float* stats,
-                                 int stats_ring, int B, hipStream_t stream) {
+                                 int stats_ring, int B, hipStream_t stream, float* partials) {
   using namespace mlplb;
   check_batch("mlp_lb_reduce", B);
   if (S < 1 || (reinterpret_cast<uintptr_t>(planes) & 15))
     throw std::runtime_error("mlp_lb_reduce: needs S >= 1 planes at a 16-byte aligned address");
-  hipLaunchKernelGGL(mlp_lb_reduce_kernel, dim3((NV4 + 255) / 256), dim3(256), 0, stream, planes,
-                     S, grad, ctr, stats, stats_ring, B);
+  const dim3 grid((NV4 + 255) / 256);
+  if (partials)
+    hipLaunchKernelGGL(mlp_lb_reduce_kernel<true>, grid, dim3(256), 0, stream, planes, S, grad,
+                       ctr, stats, stats_ring, B, partials);
+  else
+    hipLaunchKernelGGL(mlp_lb_reduce_kernel<false>, grid, dim3(256), 0, stream, planes, S, grad,
+                       ctr, stats, stats_ring, B, partials);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

@@ -543,11 +543,12 @@ void mlp_lbh_wgrad_launch(const unsigned short* xh, float* ws, int B, hipStream_
 }
 
 void mlp_lbh_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
-                           int B, hipStream_t stream) {
+                           int B, hipStream_t stream, float* partials) {
   using namespace mlplbh;
   check_batch("mlp_lbh_reduce", B);
   const LbhLayout L = lbh_layout(B);
-  mlp_lb_reduce_planes_launch(ws + L.planes, L.S, grad, ctr, stats, stats_ring, B, stream);
+  mlp_lb_reduce_planes_launch(ws + L.planes, L.S, grad, ctr, stats, stats_ring, B, stream,
+                              partials);
 }
 
 }  // namespace dtfx

@@ -177,11 +177,17 @@ void mlp_lb_slices(int B, int* S, int* R);
 void mlp_lb_fwdhead_launch(const float* p, const float* x, const int* labels, float* ws, int B,
                            int act, hipStream_t stream);
 void mlp_lb_wgrad_launch(const float* x, float* ws, int B, hipStream_t stream);
+// partials (global-norm clipping, ops/clip.py): when non-null, the caller's
+// mlp_lb_reduce_partials(B) floats; every workgroup of the reduce launch then also writes the sum
+// of squares of the gradient words it stored -- what gnorm_partials_launch (f32_api.h) leaves for
+// that gradient, bit for bit.  Null launches the plain kernel.
+int mlp_lb_reduce_partials(int B);
 void mlp_lb_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
-                          int B, hipStream_t stream);
+                          int B, hipStream_t stream, float* partials = nullptr);
 // the same launch on S planes at `planes` (16-byte aligned): what mlp_lb_reduce_launch calls
 void mlp_lb_reduce_planes_launch(const float* planes, int S, float* grad, int* ctr, float* stats,
-                                 int stats_ring, int B, hipStream_t stream);
+                                 int stats_ring, int B, hipStream_t stream,
+                                 float* partials = nullptr);
 
 // ---- its mixed-precision form (mlp_large_batch_bf16.hip): the same contract and batch range with
 // the dataset as row-major bf16 xh [n][784] (16-byte aligned) and the two 784-wide GEMMs on the
@@ -195,6 +201,6 @@ void mlp_lbh_fwdhead_launch(const float* p, const unsigned short* xh, const int*
                             int B, int act, hipStream_t stream);
 void mlp_lbh_wgrad_launch(const unsigned short* xh, float* ws, int B, hipStream_t stream);
 void mlp_lbh_reduce_launch(const float* ws, float* grad, int* ctr, float* stats, int stats_ring,
-                           int B, hipStream_t stream);
+                           int B, hipStream_t stream, float* partials = nullptr);
 
 }  // namespace dtfx

@@ -11,12 +11,15 @@
 //   lars     : momentum on g' = r_k (g + wd * p), r_k the segment's trust ratio
 //   lamb     : Adam's direction u, p -= lr * r_k * u   (two launches each, see below;
 //                                                 ops/layerwise.py is the definition)
+//   clip     : g *= pre * clip / max(pre |g|, clip)   (tf.clip_by_global_norm; norm partials
+//                                                 and scale, see below; ops/clip.py)
 //
 // The streaming loops are grid-stride over float4 (dwordx4) with a scalar tail.
 // `lr_ptr` / `step_ptr` (optional) let a captured hipGraph pick up a device-side
 // learning-rate schedule / step count instead of a frozen kernel argument.
 #include "common.h"
 #include "f32_api.h"
+#include "gnorm.h"
 #include "philox.h"
 
 #include <cmath>
@@ -280,13 +283,7 @@ __device__ __forceinline__ void lw_store(float* __restrict__ x, const LwWork& w,
   if (w.nv > 2) x[w.i + 2] = r.z;
 }
 
-// Sum of squares of a thread's values, in element order (dead lanes are +0).
-__device__ __forceinline__ float lw_sq(float4 a) {
-  float s = a.x * a.x;
-  s = __fmaf_rn(a.y, a.y, s);
-  s = __fmaf_rn(a.z, a.z, s);
-  return __fmaf_rn(a.w, a.w, s);
-}
+// (lw_sq, the sum of squares of a thread's values in element order: gnorm.h)
 
 // The workgroup's pair of sums -> partials[block][2]: DPP tree per wave, waves in wave order.
 __device__ __forceinline__ void lw_block_sums(float a, float b, float* __restrict__ partials) {
@@ -500,6 +497,98 @@ void lamb_launch(const LwSegs& sg, float* p, const float* g, float* m, float* v,
                      step_ptr);
   hipLaunchKernelGGL(lamb_apply_kernel, grid, dim3(256), 0, s, sg, p, m, v, partials, lr, lr_ptr,
                      lb1, lb2, eps, wd, step, step_ptr);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
+// Clipping by the global norm (ops/clip.py has the definition): g *= clip / max(|g|, clip), |g|
+// the Euclidean norm of the WHOLE flat gradient, fused with the gradient averaging the
+// all-reduce engine does anyway (`pre` = 1 / world): the norm of pre * g is pre * |g|, so the
+// partial sums may be taken from the unscaled buffer and ONE multiplier does both.
+//
+// The layer-wise geometry with the buffer as one segment: a workgroup of 256 threads owns 1,024
+// consecutive elements, one float4 per thread, the ragged end through lw_load / lw_store.
+//
+//   gnorm_partials : sum of squares per workgroup -> partials[block] (gnorm.h: element order,
+//     fixed DPP tree, waves in wave order; elements past n contribute +0).  The large-batch
+//     reduce launch writes the same partials for the gradient it stores (mlp_large_batch.hip,
+//     CLIP instantiation: the same geometry, the same bits), and this launch is then skipped.
+//   clip_scale : every WAVE re-adds all nblk partials itself -- lane-strided in block order, then
+//     the fixed tree, as lw_segment_sums does (the MLP's gradient has 78: a second trip for 14
+//     lanes) -- and forms norm = pre * sqrtf(sum) and the multiplier f = pre * clip / max(norm,
+//     clip) once: one IEEE division, so pre = 1 and norm <= clip give exactly 1.0f and the
+//     gradient's bits do not move.  A NaN norm takes max()'s other operand (f = pre): the
+//     non-finite elements stay non-finite, no special case.  One lane stores the norm.
+//
+// The re-add is O(nblk) loads per wave: meant for gradients of up to a few million elements.
+// Launchers allocate nothing, clear nothing and never synchronise.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ LwWork gn_work(long long n) {
+  LwWork w;
+  w.seg = 0;
+  w.blk0 = 0;
+  w.blk1 = (int)gridDim.x;
+  w.i = (long long)blockIdx.x * kLwBlock + 4 * (int)threadIdx.x;
+  const long long left = n - w.i;
+  w.nv = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
+  return w;
+}
+
+__global__ __launch_bounds__(256) void gnorm_partials_kernel(long long n,
+                                                             const float* __restrict__ g,
+                                                             float* __restrict__ partials) {
+  gn_block_sum(lw_sq(lw_load(g, gn_work(n))), partials);
+}
+
+__global__ __launch_bounds__(256) void clip_scale_kernel(long long n, float* __restrict__ g,
+                                                         const float* __restrict__ partials,
+                                                         int nblk, float clip, float pre,
+                                                         float* __restrict__ gnorm_out) {
+  const LwWork w = gn_work(n);
+  float s = 0.f;
+  for (int j = lane_id(); j < nblk; j += kWave) s += partials[j];  // block order per lane
+  s = wave_sum(s);
+  const float norm = __fmul_rn(pre, sqrtf(s));
+  const float f = __fdiv_rn(__fmul_rn(pre, clip), fmaxf(norm, clip));
+  if (gnorm_out && blockIdx.x == 0 && threadIdx.x == 0) *gnorm_out = norm;
+  if (w.nv == 0) return;
+  float4 v = lw_load(g, w);
+  v.x *= f;
+  v.y *= f;
+  v.z *= f;
+  v.w *= f;
+  lw_store(g, w, v);
+}
+
+int gnorm_blocks(long long n) {
+  if (n < 1 || n > 0x7fffffffLL - kLwBlock)
+    throw std::runtime_error("gnorm: the buffer must have 1 .. 2^31 - 1025 elements, got " +
+                             std::to_string(n));
+  return (int)((n + kLwBlock - 1) / kLwBlock);
+}
+
+void gnorm_partials_launch(long long n, const float* g, float* partials, hipStream_t s) {
+  const int nblk = gnorm_blocks(n);
+  if (!g || !partials) throw std::runtime_error("gnorm_partials: null buffer");
+  check_align(g, "gnorm_partials");
+  hipLaunchKernelGGL(gnorm_partials_kernel, dim3((unsigned)nblk), dim3(256), 0, s, n, g, partials);
+  DTFX_HIP_CHECK(hipGetLastError());
+}
+
+void clip_scale_launch(long long n, float* g, const float* partials, int nblk, float clip,
+                       float pre, float* gnorm_out, hipStream_t s) {
+  if (nblk != gnorm_blocks(n))
+    throw std::runtime_error("clip_scale: " + std::to_string(n) + " elements have " +
+                             std::to_string(gnorm_blocks(n)) + " partial sums, got " +
+                             std::to_string(nblk));
+  if (!g || !partials) throw std::runtime_error("clip_scale: null buffer");
+  if (!(clip > 0.f) || !std::isfinite(clip))
+    throw std::runtime_error("clip_scale: clip_norm must be finite and > 0");
+  if (!(pre > 0.f) || !std::isfinite(pre))
+    throw std::runtime_error("clip_scale: the pre-scale must be finite and > 0");
+  check_align(g, "clip_scale");
+  hipLaunchKernelGGL(clip_scale_kernel, dim3((unsigned)nblk), dim3(256), 0, s, n, g, partials,
+                     nblk, clip, pre, gnorm_out);
   DTFX_HIP_CHECK(hipGetLastError());
 }
 

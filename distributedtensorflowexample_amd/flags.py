@@ -220,6 +220,12 @@ def define_reference_flags(flag_values=FLAGS):
     DEFINE_float("lars_eta", 0.001,
                  "--optimizer lars: the trust coefficient eta (finite, > 0) of r = eta |p| / "
                  "(|g| + weight_decay |p|)", fv)
+    DEFINE_float("clip_norm", 0.0,
+                 "clip the averaged gradient by its global norm before the optimizer "
+                 "(tf.clip_by_global_norm, ops/clip.py): g *= clip_norm / max(|g|, clip_norm) over "
+                 "all parameters; finite and > 0, 0 = off.  --strategy mirrored --model mlp only "
+                 "(the gradient-buffer engine on any number of GPUs, every --optimizer; --device "
+                 "cpu); not with --zero1, ps_async or --model bert|resnet50", fv)
     DEFINE_float("momentum", 0.9, "--optimizer momentum | lars: the momentum", fv)
     DEFINE_float("adam_beta1", 0.9, "--optimizer adam: beta1", fv)
     DEFINE_float("adam_beta2", 0.999, "--optimizer adam: beta2", fv)

@@ -82,10 +82,30 @@ class LargeBatchWorkspace:
                     dz1h=self.buf[dz1h:planes].view(torch.bfloat16).view(BP32, 112))
 
 
-def step_grad(p, x, labels, ws: LargeBatchWorkspace, grad, stats=True, activation="sigmoid"):
+def reduce_partials(B):
+    """Workgroups of the reduce launch = floats of ``step_grad``'s ``partials`` (78 at every B)."""
+    return int(hip().mlp_lb_reduce_partials(int(B)))
+
+
+def _check_partials(partials, B):
+    if partials is None:
+        return 0
+    if (not torch.is_tensor(partials) or not partials.is_cuda or partials.dtype != torch.float32
+            or not partials.is_contiguous() or partials.numel() < reduce_partials(B)):
+        raise ValueError("partials must be a contiguous f32 GPU tensor of at least %d floats"
+                         % reduce_partials(B))
+    return ptr(partials)
+
+
+def step_grad(p, x, labels, ws: LargeBatchWorkspace, grad, stats=True, activation="sigmoid",
+              partials=None):
     """Forward/backward of the batch (x [B,784], labels [B]) at the parameters ``p``, writing the
     flat gradient ``grad``, the step's (loss, accuracy) into ``ws.stats[global_step % ring]`` (with
-    ``stats``) and advancing ``ws.ctr``.  ``activation``: ``ops/hidden_act.py``.  Returns ``p``."""
+    ``stats``) and advancing ``ws.ctr``.  ``activation``: ``ops/hidden_act.py``.  ``partials``
+    (``reduce_partials(B)`` floats, for ``ops.optim.clip_by_global_norm_(have_partials=True)``):
+    the reduce launch also leaves each workgroup's sum of squares of the gradient it stored, what
+    ``gnorm_partials`` would compute from ``grad``; ``None`` launches today's reduce.  Returns
+    ``p``."""
     if not isinstance(ws, LargeBatchWorkspace) or ws.bf16:
         raise ValueError("the large-batch step needs a LargeBatchWorkspace (bf16=False)")
     mlp_step._check(x, labels, ws.B)
@@ -95,18 +115,21 @@ def step_grad(p, x, labels, ws: LargeBatchWorkspace, grad, stats=True, activatio
     if grad.data_ptr() % 16:
         raise ValueError("the gradient buffer must be 16-byte aligned")
     act = hidden_act.act_id(activation)
+    pp = _check_partials(partials, ws.B)
     h, s = hip(), stream_handle()
     h.mlp_lb_fwdhead(ptr(p), ptr(x), ptr(labels), ptr(ws.buf), ws.B, act, s)
     h.mlp_lb_wgrad(ptr(x), ptr(ws.buf), ws.B, s)
     h.mlp_lb_reduce(ptr(ws.buf), ptr(grad), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
-                    ws.stats_ring, ws.B, s)
+                    ws.stats_ring, ws.B, s, pp)
     return p
 
 
-def step_grad_bf16(p, xh, labels, ws: LargeBatchWorkspace, grad, stats=True, activation="sigmoid"):
+def step_grad_bf16(p, xh, labels, ws: LargeBatchWorkspace, grad, stats=True, activation="sigmoid",
+                   partials=None):
     """``step_grad`` with the batch as bf16 rows ``xh`` [B,784] (contiguous, 16-byte aligned) and
     ``ws`` a ``LargeBatchWorkspace(bf16=True)``: bf16 operands and f32 accumulation in the two
-    784-wide GEMMs, everything else -- the f32 parameters ``p`` included -- as ``step_grad``."""
+    784-wide GEMMs, everything else -- the f32 parameters ``p`` and ``partials`` included -- as
+    ``step_grad``."""
     if not isinstance(ws, LargeBatchWorkspace) or not ws.bf16:
         raise ValueError("the bf16 large-batch step needs a LargeBatchWorkspace(bf16=True)")
     if (not torch.is_tensor(xh) or xh.dtype != torch.bfloat16 or not xh.is_cuda
@@ -121,9 +144,10 @@ def step_grad_bf16(p, xh, labels, ws: LargeBatchWorkspace, grad, stats=True, act
     if grad.data_ptr() % 16:
         raise ValueError("the gradient buffer must be 16-byte aligned")
     act = hidden_act.act_id(activation)
+    pp = _check_partials(partials, ws.B)
     h, s = hip(), stream_handle()
     h.mlp_lbh_fwdhead(ptr(p), ptr(xh), ptr(labels), ptr(ws.buf), ws.B, act, s)
     h.mlp_lbh_wgrad(ptr(xh), ptr(ws.buf), ws.B, s)
     h.mlp_lbh_reduce(ptr(ws.buf), ptr(grad), ptr(ws.ctr), ptr(ws.stats) if stats else 0,
-                     ws.stats_ring, ws.B, s)
+                     ws.stats_ring, ws.B, s, pp)
     return p

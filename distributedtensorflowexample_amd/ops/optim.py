@@ -169,6 +169,52 @@ def ema_(shadow, p, decay, num_updates=False, step=0, step_tensor=None):
     return shadow
 
 
+def clip_by_global_norm_(g, clip_norm, partials, pre=1.0, gnorm=None, have_partials=False):
+    """Clipping by the global norm (``ops/clip.py``), in place on the flat gradient ``g``, fused
+    with the averaging ``scale_`` does: ``g *= pre * clip_norm / max(norm, clip_norm)``, ``norm =
+    pre * |g|`` (so ``norm <= clip_norm`` and ``pre == 1`` leave ``g``'s bits alone).  ``gnorm``
+    (optional, one f32) receives ``norm``.  GPU: ``partials`` is scratch of
+    ``clip.num_partials(g.numel())`` floats (``None`` allocates it; a caller that captures a graph
+    brings its own), filled by one launch and re-added by the scale launch;
+    ``have_partials=True`` skips the first launch -- the large-batch reduce launch already left the
+    sums of squares of this very gradient there (``mlp_large_batch.step_grad(partials=...)``)."""
+    from . import clip as clip_mod
+
+    c = clip_mod.resolve(clip_norm)
+    if c is None:
+        raise ValueError("clip_by_global_norm_: clip_norm must be > 0 (0 is no clipping: do not "
+                         "call)")
+    pre = float(pre)
+    if not (pre > 0.0 and pre < float("inf")):
+        raise ValueError("clip_by_global_norm_: pre must be finite and > 0, got %r" % (pre,))
+    if not g.is_cuda:
+        with torch.no_grad():
+            norm = g.norm() * pre
+            if gnorm is not None:
+                gnorm.fill_(float(norm))
+            g.mul_(pre * c / max(float(norm), c))
+        return g
+    check_gpu_f32(g, gnorm)
+    n, nb = g.numel(), clip_mod.num_partials(g.numel())
+    if g.data_ptr() % 16:
+        raise ValueError("clip_by_global_norm_: the gradient must be 16-byte aligned")
+    if partials is None:
+        if have_partials:
+            raise ValueError("clip_by_global_norm_: have_partials needs the partials")
+        partials = torch.empty(nb, device=g.device, dtype=torch.float32)
+    check_gpu_f32(partials)
+    if partials.numel() < nb:
+        raise ValueError("clip_by_global_norm_: partials must hold one float for each of the %d "
+                         "workgroups (got %d)" % (nb, partials.numel()))
+    if gnorm is not None and gnorm.numel() < 1:
+        raise ValueError("clip_by_global_norm_: gnorm must hold one float")
+    h, s = hip(), stream_handle()
+    if not have_partials:
+        h.gnorm_partials(n, ptr(g), ptr(partials), s)
+    h.clip_scale(n, ptr(g), ptr(partials), nb, c, pre, ptr(gnorm), s)
+    return g
+
+
 def scale_(x, a):
     if not x.is_cuda:
         x.mul_(a)

@@ -167,6 +167,22 @@ a host->GPU feed of 317 KB and ~14 tiny TF kernels.  Here:
   ``[m, v]``) and the segment table.  Schedules, the moving average, activations, shuffle, the
   ``allreduce`` hook, ``compute_dtype="bf16"`` and (up to 256 rows) dropout compose unchanged;
   the exchange engines, ``pipeline=False`` and the persistent launch refuse them.
+* ``clip_norm`` (``--clip_norm``; ``ops/clip.py`` has the definition, which is
+  ``tf.clip_by_global_norm``'s): the averaged gradient is scaled by ``clip_norm / max(norm,
+  clip_norm)``, ``norm`` its Euclidean norm over all 79,510 elements, BEFORE weight decay,
+  momentum, the Adam moments and the LARS / LAMB trust ratios see it.  Like lars / lamb it needs
+  the gradient in memory, so a non-zero value selects the gradient-buffer engine at every batch
+  size, plain sgd included (``pipelined``, ``direct`` and ``host_loop_ok`` are false; every
+  update is applied in place).  The ``1 / world`` averaging and the clip are one multiplier, so
+  ``csrc/kernels/optim.hip``'s ``clip_scale`` runs in place of ``scale_``.  The sums of squares
+  it re-adds (one per 1,024 elements, fixed order, no atomics) come from the large-batch reduce
+  launch itself above 256 rows without an ``allreduce`` hook -- no launch added -- and from one
+  ``gnorm_partials`` launch on the reduced gradient otherwise.  ``grad_norm`` (one device float)
+  holds the pre-clip norm of the last applied step; nothing reads it back on the hot path.
+  Composes with every optimizer, schedule, decay, moving average, activation, shuffle,
+  ``compute_dtype`` and (up to 256 rows) dropout; the exchange engines, ``pipeline=False``,
+  ``run_launched`` and the persistent launch refuse it.  ``clip_norm=0`` launches exactly
+  today's kernels.
 
 Data-parallel update order: the all-reduced gradient of step t is applied at
 the start of step t+1 (ping-pong parameter buffers make the apply race-free
@@ -180,6 +196,7 @@ import time
 
 import torch
 
+from ..ops import clip as clip_mod
 from ..ops import dropout as dropout_mod
 from ..ops import ema as ema_mod
 from ..ops import hidden_act
@@ -198,7 +215,19 @@ class FusedMLPTrainer:
                  shuffle=False, shuffle_seed=0, optimizer="sgd", momentum=0.9, beta1=0.9,
                  beta2=0.999, epsilon=1e-8, lr_schedule=None, dropout=0.0, dropout_seed=0,
                  weight_decay=0.0, adamw=True, nesterov=False, activation="sigmoid",
-                 ema_decay=0.0, ema_num_updates=False, compute_dtype="fp32", lars_eta=0.001):
+                 ema_decay=0.0, ema_num_updates=False, compute_dtype="fp32", lars_eta=0.001,
+                 clip_norm=0.0):
+        # --clip_norm: refused first where no launch holds the whole gradient
+        self.clip = clip_mod.resolve(clip_norm)
+        if self.clip is not None:
+            if fused_comm is not None or factor_comm is not None:
+                raise ValueError("clip_norm: the exchange engines (fused_comm / factor_comm) never "
+                                 "hold the averaged gradient to take the norm of; use the "
+                                 "all-reduce engine")
+            if not pipeline and allreduce is None and int(world_size) == 1:
+                raise ValueError("clip_norm: the three-launch direct step (pipeline=False) applies "
+                                 "the gradient inside the launch that forms it; clipping selects "
+                                 "the gradient-buffer engine itself (pipeline=True)")
         # --ema_decay: refused first where no launch carries a shadow plane
         self.avg = ema_mod.resolve(ema_decay, ema_num_updates)
         if self.avg is not None:
@@ -361,9 +390,9 @@ class FusedMLPTrainer:
         # <= 128): the two-launch pipelined step
         # (batch_size > 256: the large-batch engine is neither pipelined nor direct)
         # (lars / lamb: a layer-wise rule takes norms of the gradient, and the two-launch step
-        # never holds one -- the gradient-buffer engine at every batch size)
+        # never holds one -- the gradient-buffer engine at every batch size; clip_norm the same)
         self.pipelined = bool(pipeline and not self.large and self.lw is None
-                              and allreduce is None and (
+                              and self.clip is None and allreduce is None and (
             (self.world_size == 1 and factor_comm is None and fused_comm is None)
             or fused_comm is not None
             or (factor_comm is not None and self.B <= 128)))
@@ -385,6 +414,17 @@ class FusedMLPTrainer:
             self.segments = layerwise_mod.mlp_segments()
             self._partials = torch.zeros(2 * layerwise_mod.num_blocks(self.segments),
                                          device=self.device, dtype=torch.float32)
+        # clip_norm: the partial sums of squares (one per 1,024 gradient elements) and the
+        # pre-clip norm of the last applied step.  Above 256 rows without an all-reduce hook the
+        # reduce launch that stores the gradient fills the partials (no launch added); with a
+        # hook, or up to 256 rows, gnorm_partials runs on the reduced gradient after the hook
+        self.grad_norm = self._clip_partials = self._reduce_partials = None
+        if self.clip is not None:
+            self.grad_norm = torch.zeros(1, device=self.device, dtype=torch.float32)
+            self._clip_partials = torch.zeros(clip_mod.num_partials(mlp_step.NPARAM),
+                                              device=self.device, dtype=torch.float32)
+            if self.large and allreduce is None:
+                self._reduce_partials = self._clip_partials
         # the all-reduce engine's scheduled rate (ops.optim's lr_tensor)
         self._lr_dev = (torch.zeros(1, device=self.device, dtype=torch.float32)
                         if self.sched is not None else None)
@@ -418,7 +458,7 @@ class FusedMLPTrainer:
     @property
     def direct(self):
         """SGD apply fused into the backward kernel (one GPU, or the fused xGMI exchange)."""
-        return not self.pipelined and not self.large and self.lw is None and (
+        return not self.pipelined and not self.large and self.lw is None and self.clip is None and (
             self.fused_comm is not None or self.factor_comm is not None
             or (self.allreduce is None and self.world_size == 1))
 
@@ -440,6 +480,10 @@ class FusedMLPTrainer:
         """The optimizer's slot planes (momentum: [accum]; adam: [m, v]; sgd: []), flat f32
         [79510] in the parameter layout -- like ``params``, without a pending update."""
         self._verified()
+        return self._slots
+
+    @property
+    def _slots(self):
         return [] if self.opt is None else self.opt.slots
 
     def load_slots(self, slots):
@@ -472,8 +516,10 @@ class FusedMLPTrainer:
     @property
     def _inplace(self):
         """All-reduce engine with an optimizer: the reduced gradient is applied in place on the
-        current buffer (``ops.optim``), so the parity never moves."""
-        return self.opt is not None and not self.pipelined
+        current buffer (``ops.optim``), so the parity never moves.  ``clip_norm`` alone (plain
+        sgd) applies in place too: the deferred apply inside the next step's launches has no
+        clipped form."""
+        return (self.opt is not None or self.clip is not None) and not self.pipelined
 
     def _apply_reduced(self, p, slots, publish=True, shadow=None):
         """The pending all-reduced gradient through the optimizer, in place on ``p`` /
@@ -482,8 +528,18 @@ class FusedMLPTrainer:
         the pending step's rate -- step ``counter - 1`` -- is computed on the device first and
         read by the optimizer kernel (``publish``: also written to the rate ring).  With a
         moving average ``shadow`` (default: the trainer's own) then follows the new ``p``
-        (``ops.optim.ema_``; its t is the same counter)."""
-        optim.scale_(self.grad, 1.0 / self.world_size)
+        (``ops.optim.ema_``; its t is the same counter).  With ``clip_norm`` the averaging launch
+        is the clip launch (``ops/clip.py``: one multiplier does both), so every rule below sees
+        the clipped gradient; ``grad_norm`` receives the pre-clip norm."""
+        if self.clip is not None:
+            optim.clip_by_global_norm_(self.grad, self.clip, self._clip_partials,
+                                       pre=1.0 / self.world_size, gnorm=self.grad_norm,
+                                       have_partials=self._reduce_partials is not None)
+        else:
+            optim.scale_(self.grad, 1.0 / self.world_size)
+        if self.opt is None:  # (clip_norm with plain sgd at a constant rate)
+            optim.sgd_(p, self.grad, self.lr)
+            return
         h = self.opt.hyper
         lrt = None
         if self.sched is not None:
@@ -533,8 +589,8 @@ class FusedMLPTrainer:
                 mlp_step.flush_pipelined(self.bufs[self.cur], self.bufs[self.cur ^ 1], xp, self.ws,
                                          self.lr)
                 self.cur ^= 1
-            elif self.opt is not None:
-                self._apply_reduced(self.bufs[self.cur], self.opt.slots)
+            elif self._inplace:
+                self._apply_reduced(self.bufs[self.cur], self._slots)
             else:
                 optim.sgd_(self.bufs[self.cur], self.grad, self.lr / self.world_size)
             self.pending = False
@@ -559,9 +615,11 @@ class FusedMLPTrainer:
                                "(ema_decay is 0)")
         if with_slots or with_ema:
             if self.pending and self._inplace:
-                out, sl = self.bufs[self.cur].clone(), [t.clone() for t in self.opt.slots]
+                out, sl = self.bufs[self.cur].clone(), [t.clone() for t in self._slots]
                 sh = self.opt.shadow.clone() if self.avg is not None else None
-                g = self.grad.clone()  # (_apply_reduced scales the gradient in place)
+                # (_apply_reduced scales / clips the gradient in place; the partial sums the
+                # reduce launch left describe the restored gradient, so they stay valid)
+                g = self.grad.clone()
                 # (the rate ring and the trainer's shadow do not move)
                 self._apply_reduced(out, sl, publish=False, shadow=sh)
                 self.grad.copy_(g)
@@ -723,17 +781,20 @@ class FusedMLPTrainer:
         if self.large:
             # large-batch engine: the pending gradient in place (plain sgd as flush() does),
             # then the three large-batch launches; the parity never moves
-            if self.pending and self.opt is not None:
-                self._apply_reduced(cur, self.opt.slots)
+            if self.pending and self._inplace:
+                self._apply_reduced(cur, self._slots)
             elif self.pending:
                 optim.sgd_(cur, self.grad, self.lr / self.world_size)
+            # (clip_norm without an all-reduce hook: the reduce launch also leaves the partial
+            # sums of squares of the gradient it stores; None launches the plain reduce)
             (mlp_large_batch.step_grad_bf16 if self.bf16 else mlp_large_batch.step_grad)(
-                cur, xb, yb, self.ws, self.grad, activation=self.activation)
-        elif self.opt is not None:
-            # all-reduce engine with an optimizer: the reduced gradient of the previous step
-            # through ops.optim in place, then the step without its deferred apply
+                cur, xb, yb, self.ws, self.grad, activation=self.activation,
+                partials=self._reduce_partials)
+        elif self._inplace:
+            # all-reduce engine with an optimizer (or clip_norm): the reduced gradient of the
+            # previous step through ops.optim in place, then the step without its deferred apply
             if self.pending:
-                self._apply_reduced(cur, self.opt.slots)
+                self._apply_reduced(cur, self._slots)
             mlp_step.step_grad(cur, xb, yb, self.ws, self.grad, dropout=self.drop,
                                activation=self.activation)
         elif self.pending:
@@ -808,6 +869,9 @@ class FusedMLPTrainer:
         the Python side of this call before its first kernel starts."""
         steps = int(steps)
         if not self.host_loop_ok:
+            if self.clip is not None:
+                raise ValueError("clip_norm: run_launched issues the two-launch step, which never "
+                                 "holds a gradient to clip; use run()")
             raise RuntimeError("run_launched: pipelined single-GPU step or exchange engine only")
         if steps <= 0:
             if flush:
@@ -884,6 +948,9 @@ class FusedMLPTrainer:
         inside the C++ call (its x_prev is that epoch's own last batch)."""
         steps = int(steps)
         if not self.host_loop_ok:
+            if self.clip is not None:
+                raise ValueError("clip_norm: run_launched issues the two-launch step, which never "
+                                 "holds a gradient to clip; use run()")
             raise RuntimeError("run_launched: pipelined single-GPU step or exchange engine only")
         while steps > 0:
             if self.pos == 0 and self.pending:
@@ -955,6 +1022,9 @@ class FusedMLPTrainer:
             raise ValueError("run_persistent: the persistent launch keeps no moving average of "
                              "the parameters (ema_decay is not supported); use run() / "
                              "run_launched()")
+        if self.clip is not None:
+            raise ValueError("run_persistent: the persistent launch never holds a gradient to "
+                             "clip (clip_norm is not supported); use run()")
         if self.lw is not None:
             raise ValueError("run_persistent: the persistent launch applies gradient descent "
                              "only (optimizer %s needs the gradient-buffer engine); use run()"

@@ -22,6 +22,7 @@ import torch.distributed as dist
 from ..models import mlp as mlp_model
 from ..ops import dropout as dropout_mod
 from ..ops import ema as ema_mod
+from ..ops import clip as clip_mod
 from ..ops import layerwise as layerwise_mod
 from ..ops import hidden_act
 from ..ops import lr_schedule, mlp_step, nn, optim
@@ -74,6 +75,13 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
     if lw is not None and getattr(flags, "zero1", False):
         layerwise_mod.refuse(flags, "--zero1 (a sharded owner sees a slice of a tensor, not its "
                                     "norm)")
+    # --clip_norm (ops/clip.py): the averaged gradient clipped by its global norm before the
+    # optimizer -- the fused trainer's gradient-buffer engine on the GPU, ops.optim's CPU branch on
+    # the autograd path; no new state, so checkpoints hold nothing new
+    clip_norm = clip_mod.from_flags(flags)
+    if clip_norm is not None and getattr(flags, "zero1", False):
+        clip_mod.refuse(flags, "--zero1 (a sharded owner sees a slice of the gradient, not its "
+                               "norm)")
     if opt_kind != "sgd" and getattr(flags, "zero1", False):
         raise ValueError("--optimizer %s does not support --zero1: the sharded update applies "
                          "gradient descent only" % opt_kind)
@@ -174,12 +182,13 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
         pipe = True
         if (comm is not None and os.environ.get("DTFX_MLP_COMM", "auto") != "rccl"
                 and opt_kind == "sgd" and sched is None and drop is None and decay is None
-                and act == "sigmoid" and avg is None and B <= mlp_step.MAX_BATCH):
+                and act == "sigmoid" and avg is None and clip_norm is None
+                and B <= mlp_step.MAX_BATCH):
             # exchange engine (fused into the backward kernel / factor all-gather) when
             # verified and faster than the all-reduce engine (sgd at a constant rate without
             # dropout or weight decay and the sigmoid head only: with an optimizer, a schedule,
-            # --dropout, --weight_decay, --activation relu | tanh or --ema_decay the all-reduce
-            # engine it is)
+            # --dropout, --weight_decay, --activation relu | tanh, --ema_decay or --clip_norm the
+            # all-reduce engine it is)
             from ..parallel.select import pick_mlp_engine
 
             if world <= 8:
@@ -208,7 +217,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                              ema_decay=avg.decay if avg else 0.0,
                              ema_num_updates=avg.num_updates if avg else False,
                              compute_dtype="bf16" if dtype == "bf16" else "fp32",
-                             lars_eta=lw.eta if lw else layerwise_mod.DEFAULT_ETA, **opt_kw)
+                             lars_eta=lw.eta if lw else layerwise_mod.DEFAULT_ETA,
+                             clip_norm=clip_norm or 0.0, **opt_kw)
         # tr.snapshot() never starts a peer exchange on ONE rank and never changes the
         # replicas' update sequence (the all-reduce engine's pending gradient is applied to a
         # copy); the pipelined exchange engines have nothing pending at the checkpoint /
@@ -270,6 +280,8 @@ def train_mirrored(flags, dataset, log=print, max_steps=None):
                   else float(sched.value_f32(flags.learning_rate, i)))
             state["rates"].append(lr)
             with torch.no_grad():
+                if clip_norm is not None:  # first: every rule below sees the clipped gradient
+                    optim.clip_by_global_norm_(g, clip_norm, None)
                 if opt_kind == "momentum":
                     optim.momentum_(model.flat.data, g, cpu_slots[0], lr,
                                     momentum=opt_kw["momentum"],

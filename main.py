@@ -87,6 +87,20 @@ def main(argv=None):
         layerwise.from_flags(FLAGS)
     except ValueError as e:
         raise SystemExit(str(e))
+    # --clip_norm: the mirrored MLP's gradient-buffer engine only (ops/clip.py)
+    from distributedtensorflowexample_amd.ops import clip
+
+    try:
+        if FLAGS.strategy != "mirrored":
+            clip.refuse(FLAGS, "--strategy ps_async (--ps_device cpu and gpu)")
+        elif FLAGS.model != "mlp":
+            clip.refuse(FLAGS, "--model %s" % FLAGS.model)
+        elif getattr(FLAGS, "zero1", False):
+            clip.refuse(FLAGS, "--zero1 (a sharded owner sees a slice of the gradient, not its "
+                               "norm)")
+        clip.from_flags(FLAGS)
+    except ValueError as e:
+        raise SystemExit(str(e))
     if FLAGS.strategy == "mirrored" and FLAGS.optimizer != "sgd":
         # --optimizer momentum | adam: the fused MLP trainer's and the GPU parameter store's
         # (train/worker.py validates the ps_async combinations); never silently ignored
