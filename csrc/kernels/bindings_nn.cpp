@@ -374,6 +374,18 @@ void register_nn(py::module_& m) {
      py::arg("nseg") = 0,
      "segs (int64 [nseg][5]: lo4, hi4, planes, plane stride in float4s, S): ranges whose "
      "gradient is the sum of S split-K planes (conv_bf16 defer_reduce), summed here");
+  m.def("lars_mixed_chunk", &dtfx::lars_mixed_chunk, "elements per workgroup of lars_momentum_mixed");
+  m.def("lars_momentum_mixed", [](long long n, uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t pb,
+                                  float lr, float mu, float wd, float eta, float gscale,
+                                  uintptr_t tab_host, uintptr_t tab_dev, int ntensor, int nwg,
+                                  uintptr_t partials, uintptr_t s) {
+    dtfx::lars_momentum_mixed_launch(n, P<float>(p), P<float>(g), P<float>(v), P<void>(pb), lr, mu,
+                                     wd, eta, gscale, P<const long long>(tab_host),
+                                     P<const long long>(tab_dev), ntensor, nwg, P<float>(partials),
+                                     S(s));
+  }, "LARS (1-D tensors excluded) on the f32 master + bf16 copy: norms launch + apply launch over "
+     "a tensor-aligned grid; tab_host / tab_dev: the same int64 table (8 words per tensor, one "
+     "per workgroup) in host and device memory, partials: 2 floats per workgroup");
   m.def("flash_fwd", [](int Bn, int Sq, int nh, uintptr_t qkv, uintptr_t out, uintptr_t lse,
                         int ld_lse, uintptr_t kmask, float scale, uintptr_t s) {
     dtfx::flash_fwd_launch(Bn, Sq, nh, P<const void>(qkv), P<void>(out), P<float>(lse), ld_lse,

@@ -128,6 +128,14 @@ void sgd_momentum_mixed_launch(long long n, float* p, const float* g, float* v, 
                                float mu, float wd, float gscale, hipStream_t st,
                                const long long* segs, int nseg);
 
+// ---- lars_mixed.hip (LARS over every tensor of the mixed-precision flat buffer, two launches;
+// the table's layout is in the file header, tab_host / tab_dev are the same words)
+int lars_mixed_chunk();
+void lars_momentum_mixed_launch(long long n, float* p, float* g, float* v, void* pb, float lr,
+                                float mu, float wd, float eta, float gscale,
+                                const long long* tab_host, const long long* tab_dev, int ntensor,
+                                int nwg, float* partials, hipStream_t st);
+
 // ---- stem_conv.hip
 bool stem_conv_applies(int H, int W, int C, int Cout, int KH, int KW, int stride, int pad);
 int stem_conv_fwd_rows(int N, int OH, int OW);

@@ -216,7 +216,11 @@ def define_reference_flags(flag_values=FLAGS):
                   "scaled by a trust ratio of norms computed by two HIP launches after the "
                   "gradient; lars is momentum SGD (--momentum, --lars_eta), lamb is Adam "
                   "(--adam_*); --weight_decay is part of both rules; not with --nesterov, "
-                  "--noadamw, --zero1, ps_async or --model bert|resnet50", fv)
+                  "--noadamw, --zero1, ps_async or --model bert.  --model resnet50 takes lars "
+                  "(not lamb): every tensor of its flat buffer in two HIP launches of its own, "
+                  "BatchNorm scales / offsets and biases excluded from the trust ratio and the "
+                  "decay, the trainer's own weight decay in the rule (--lars_eta, --momentum; "
+                  "--device cpu; not with --zero1)", fv)
     DEFINE_float("lars_eta", 0.001,
                  "--optimizer lars: the trust coefficient eta (finite, > 0) of r = eta |p| / "
                  "(|g| + weight_decay |p|)", fv)

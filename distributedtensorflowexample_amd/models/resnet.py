@@ -175,6 +175,7 @@ class ResNet50:
         self._fold = False   # enable_splitk_fold
         self._planes = {}    # conv name -> its persistent split-K planes (0: not folded)
         self._segs = None    # the optimizer's segment table (int64 [n][5])
+        self._lars = None    # (folded convs, ops.cnn.LarsTable) of lars_step
 
     # conv + fused BN statistics (column sums in the conv epilogue)
     def _conv_bn(self, name, x):
@@ -558,6 +559,36 @@ class ResNet50:
         p = self.params
         CN.sgd_momentum_mixed(p.master, p.grad, p.mom, p.bf, lr, momentum, wd, gscale,
                               segs=self._segs)
+
+    def lars_tensors(self):
+        """``(start, length, adapted[, planes, plane stride, S, plane length])`` per tensor of
+        the flat buffer, for :class:`ops.cnn.LarsTable`: a tensor's record runs to the next one's
+        start (its alignment padding, zero for ever, belongs to it), tensors with 2 or more
+        dimensions are adapted, and a folded convolution names its split-K planes."""
+        p = self.params
+        names = [name for name, _, _ in p.layout]
+        starts = [p.offsets[n][0] for n in names] + [p.numel]
+        rows = []
+        for k, name in enumerate(names):
+            row = (starts[k], starts[k + 1] - starts[k], len(p.offsets[name][1]) >= 2)
+            v = self._planes.get(name[:-len(".weight")]) if name.endswith(".weight") else None
+            if v is not None:
+                buf, off, m, S = v
+                assert off == starts[k]
+                row += (buf, m, S, m)
+            rows.append(row)
+        return rows
+
+    def lars_step(self, lr, momentum=0.9, wd=5e-5, eta=0.001, gscale=1.0):
+        """LARS over every tensor (``ops/layerwise.py: lars_mixed_update``) in two launches;
+        the momentum slot is ``params.mom``.  The table is rebuilt when a convolution's planes
+        appear (the first, eager step with the fold on)."""
+        p = self.params
+        key = sum(v is not None for v in self._planes.values())
+        if self._lars is None or self._lars[0] != key:
+            self._lars = (key, CN.LarsTable(self.lars_tensors(), self.device))
+        CN.lars_momentum_mixed(p.master, p.grad, p.mom, p.bf, lr, self._lars[1], momentum, wd,
+                               eta, gscale)
 
 
 def synthetic_imagenet(batch, device, size=224, seed=0, num_classes=NUM_CLASSES):

@@ -785,3 +785,92 @@ def sgd_momentum_mixed(p, g, v, pb, lr, momentum=0.9, wd=0.0, gscale=1.0, segs=N
         return
     hip().sgd_momentum_mixed(p.numel(), ptr(p), ptr(g), ptr(v), ptr(pb), float(lr), float(momentum),
                              float(wd), float(gscale), stream_handle())
+
+
+class LarsTable:
+    """The table ``lars_momentum_mixed`` walks, built once per flat-buffer layout.
+
+    ``tensors``: one ``(start, length, adapted[, planes, plane_stride, S, plane_len])`` per tensor,
+    in elements, tiling the buffer ``[0, n)`` in order; starts and lengths are multiples of 4.
+    ``adapted``: the tensor takes the trust ratio and the decay (2 or more dimensions); else it is
+    excluded (``r = 1``, no decay).  A folded tensor (GPU) names its ``S`` split-K planes (an f32
+    tensor or an address), ``plane_stride`` apart, covering its first ``plane_len`` elements
+    (default: all of it).  On the device the table is int64 words: 8 per tensor, then one per
+    workgroup (tensor | chunk << 32, ``CHUNK`` elements each; no workgroup straddles two tensors)
+    -- ``csrc/kernels/lars_mixed.hip`` has the layout.  ``partials``: 2 floats per workgroup,
+    allocated here unless the caller brings them."""
+
+    CHUNK = 1024
+
+    def __init__(self, tensors, device, partials=None):
+        self.device = torch.device(device)
+        self.tensors = [(int(t[0]), int(t[1]), bool(t[2])) for t in tensors]
+        self.n = sum(t[1] for t in self.tensors)
+        self._keep = []  # plane buffers the table points into
+        recs, wgs = [], []
+        for k, t in enumerate(tensors):
+            start, length, adapted = self.tensors[k]
+            planes, pstride, S, plen = (tuple(t[3:]) + (0, 0, 0, 0))[:4]
+            if torch.is_tensor(planes):
+                self._keep.append(planes)
+                planes = planes.data_ptr()
+            if S and not plen:
+                plen = length
+            recs += [start, length, int(adapted), int(planes), int(pstride), int(S), len(wgs),
+                     int(plen)]
+            wgs += [k | (c << 32) for c in range((length + self.CHUNK - 1) // self.CHUNK)]
+        self.ntensor, self.nwg = len(self.tensors), len(wgs)
+        self.host = torch.tensor(recs + wgs, dtype=torch.int64)
+        self.folded = any(recs[8 * k + 5] for k in range(self.ntensor))
+        if self.device.type == "cuda":
+            if self.CHUNK != hip().lars_mixed_chunk():
+                raise RuntimeError("LarsTable: chunk size differs from the kernels'")
+            self.dev = self.host.to(self.device)
+            if partials is None:
+                partials = torch.zeros(2 * self.nwg, device=self.device)
+            if not (partials.is_cuda and partials.dtype == torch.float32
+                    and partials.is_contiguous() and partials.numel() >= 2 * self.nwg):
+                raise ValueError("LarsTable: partials must be a contiguous f32 GPU tensor of at "
+                                 "least 2 floats per workgroup (%d)" % (2 * self.nwg))
+        else:
+            self.dev = None
+        self.partials = partials
+
+
+def lars_momentum_mixed(p, g, v, pb, lr, table, momentum=0.9, wd=0.0, eta=0.001, gscale=1.0):
+    """LARS on the f32 master (bf16 copy refreshed) over every tensor of ``table`` (a
+    :class:`LarsTable`): ``ops/layerwise.py: lars_mixed_update`` is the definition.  GPU: two
+    HIP launches (norms, apply); a folded tensor's plane sum is left in its range of ``g``.
+    CPU tensors: the same rule in plain f32 torch (no folded tensors there)."""
+    if not isinstance(table, LarsTable):
+        raise ValueError("lars_momentum_mixed: table must be a LarsTable")
+    if p.is_cuda != (table.device.type == "cuda"):
+        raise ValueError("lars_momentum_mixed: the table was built for %s" % table.device)
+    for t, dt in ((p, torch.float32), (g, torch.float32), (v, torch.float32), (pb, BF16)):
+        if t is not None and not (t.dtype == dt and t.is_contiguous() and t.device == p.device
+                                  and t.numel() == p.numel()):
+            raise ValueError("lars_momentum_mixed: p, g, v (f32) and pb (bf16) must be contiguous, "
+                             "of one size, on one device")
+    if not p.is_cuda:
+        if table.folded:
+            raise ValueError("lars_momentum_mixed: folded tensors (split-K planes) are a GPU path")
+        if table.n != p.numel():
+            raise ValueError("lars_momentum_mixed: the tensors end at %d, the buffer has %d "
+                             "elements" % (table.n, p.numel()))
+        for a, m, adapted in table.tensors:
+            pk, vk = p[a:a + m], v[a:a + m]
+            gk = g[a:a + m] * gscale
+            if adapted:
+                pn = pk.norm()
+                den = gk.norm() + wd * pn
+                r = eta * pn / den if (float(pn) > 0.0 and float(den) > 0.0) else 1.0
+                gk = r * (gk + wd * pk)
+            vk.mul_(momentum).add_(gk)
+            pk.sub_(lr * vk)
+        if pb is not None:
+            pb.copy_(p)
+        return
+    hip().lars_momentum_mixed(p.numel(), ptr(p), ptr(g), ptr(v), ptr(pb), float(lr),
+                              float(momentum), float(wd), float(eta), float(gscale),
+                              table.host.data_ptr(), table.dev.data_ptr(), table.ntensor,
+                              table.nwg, ptr(table.partials), stream_handle())

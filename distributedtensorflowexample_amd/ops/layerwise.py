@@ -24,6 +24,11 @@ On the device each rule is two launches over a segment-aligned grid (``csrc/kern
 a workgroup owns ``BLOCK`` = 1,024 consecutive elements of one segment, so a table has at most
 ``MAX_SEGMENTS`` = 8 segments, each starting at a multiple of 4 elements (only the buffer's end
 may be ragged), and the caller owns ``2 * num_blocks(segments)`` floats of partial sums.
+
+ResNet-50 (``--model resnet50 --optimizer lars``) takes the same lars rule with an exclusion list
+-- ``lars_mixed_update`` below is its definition -- through kernels of its own
+(``csrc/kernels/lars_mixed.hip``, ``ops.cnn.lars_momentum_mixed``): any number of tensors, the
+bf16 working copy and the split-K gradient planes of its flat buffer.
 """
 from __future__ import annotations
 
@@ -180,11 +185,53 @@ def from_flags(flags):
         raise ValueError("--weight_decay: %s" % e)
 
 
+def lars_mixed_update(p, g, v, lr, tensors, momentum=0.9, wd=0.0, eta=DEFAULT_ETA, gscale=1.0):
+    """The definition, in float64, of ResNet-50's LARS step (``ops.cnn.lars_momentum_mixed``)
+    -> ``(p_new, v_new)`` (new tensors; inputs untouched; the bf16 copy is ``bf16(p_new)``,
+    round-to-nearest-even).
+
+    ``tensors``: ``(start, length, adapted)`` per tensor of the flat buffer, tiling it in order;
+    ``g``: the gradient buffer, a folded tensor's range holding the sum of its split-K planes in
+    plane order.  Per tensor ``g = gscale * G``; adapted tensors (2 or more dimensions: convolution
+    and fc weights) take ``r = eta |p| / (|g| + wd |p|)`` when ``|p| > 0`` and the denominator is
+    > 0, else ``r = 1``, and ``g' = r (g + wd p)``; excluded ones (1-D: BatchNorm scales / offsets,
+    biases) take ``r = 1`` and no decay, ``g' = g``.  Then ``sgd_momentum_mixed``'s arithmetic on
+    ``g'``: ``v = mu v + g'; p -= lr v``.  No Nesterov, no clipping function.
+
+    This differs from the MLP's lars above only in the exclusion list (there every segment is
+    adapted and decayed, biases included)."""
+    import torch
+
+    f64 = torch.float64
+    p, g, v = (x.detach().to(f64).cpu() for x in (p, g, v))
+    lr, mu, wd, eta, gscale = (float(x) for x in (lr, momentum, wd, eta, gscale))
+    p_new, v_new = p.clone(), v.clone()
+    at = 0
+    for start, length, adapted in tensors:
+        a, b = int(start), int(start) + int(length)
+        if a != at or b <= a:
+            raise ValueError("lars_mixed_update: the tensors must tile the buffer in order")
+        at = b
+        gs = gscale * g[a:b]
+        if adapted:
+            pn, gn = float(p[a:b].norm()), float(gs.norm())
+            den = gn + wd * pn
+            r = eta * pn / den if (pn > 0.0 and den > 0.0) else 1.0
+            gs = r * (gs + wd * p[a:b])
+        v_new[a:b] = mu * v[a:b] + gs
+        p_new[a:b] = p[a:b] - lr * v_new[a:b]
+    if at != p.numel():
+        raise ValueError("lars_mixed_update: the tensors end at %d, the buffer has %d elements"
+                         % (at, p.numel()))
+    return p_new, v_new
+
+
 def refuse(flags, what):
-    """ValueError for a path without a norm pass (it names the one that has it)."""
+    """ValueError for a path without a norm pass (it names the ones that have it)."""
     kind = getattr(flags, "optimizer", "sgd")
     if is_layerwise(kind):
         raise ValueError("--optimizer %s: %s has no layer-wise update (it would need every "
                          "tensor's norm); it is supported by --strategy mirrored --model mlp "
-                         "(the gradient-buffer engine on any number of GPUs; --device cpu)"
+                         "(the gradient-buffer engine on any number of GPUs; --device cpu), and "
+                         "lars also by --strategy mirrored --model resnet50 (not with --zero1)"
                          % (kind, what))

@@ -50,6 +50,15 @@ def train_model_mirrored(flags, log=print):
     from ..ops import weight_decay
 
     weight_decay.refuse(flags, "--model %s (it has its own weight decay)" % flags.model)
+    from ..ops import layerwise
+
+    # --optimizer lars: ResNet-50's layer-wise step (--lars_eta, --momentum; the trainer's own
+    # wd is the rule's decay).  lamb, and either with bert, have no such path.
+    lars = layerwise.from_flags(flags) if getattr(flags, "optimizer", "sgd") == "lars" else None
+    if flags.model != "resnet50" or lars is None:
+        layerwise.refuse(flags, "--model %s" % flags.model)
+    elif getattr(flags, "zero1", False):
+        layerwise.refuse(flags, "--zero1 (a sharded owner sees a slice of a tensor, not its norm)")
     if world > 1 and not dist.is_initialized():
         init_process_group_with_timeout(  # control plane; tensors over RCCL on GPU
             "gloo", getattr(flags, "dist_timeout_secs", None))
@@ -91,7 +100,9 @@ def train_model_mirrored(flags, log=print):
         ncls = 10 if tiny else 1000
         tr = ResNetTrainer(flags.batch_size, dev, comm=comm, lr=flags.learning_rate,
                            seed=flags.seed, image_size=32 if tiny else flags.image_size,
-                           stages=stages, num_classes=ncls, data_seed=rank)
+                           stages=stages, num_classes=ncls, data_seed=rank,
+                           **(dict(optimizer="lars", lars_eta=lars.eta, momentum=lars.momentum)
+                              if lars is not None else {}))
     else:
         raise ValueError("--model must be bert or resnet50 here (mlp: train_mirrored)")
     model = tr.model

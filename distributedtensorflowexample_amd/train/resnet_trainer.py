@@ -19,6 +19,11 @@ head -- padded to ALIGN * W elements):
                   stream at the start of the step; the forward of block b waits only for
                   bucket b's gather (``on_bucket_needed``), so the gathers overlap the forward
 
+``optimizer="lars"`` (``--optimizer lars``, ``lars_eta``): the one momentum launch becomes LARS
+over every tensor in two launches (``ResNet50.lars_step``, ``ops/layerwise.py:
+lars_mixed_update``); ``wd`` is the rule's decay, ``mom`` its slot.  Not with ``zero1``: a
+shard cuts through tensors, and a tensor's norm would need every shard.
+
 Between steps the non-owned shards are one update behind: ``sync_params()`` (a collective)
 completes them for checkpoints, evals and replica checks.
 """
@@ -34,7 +39,13 @@ from ..models.resnet import STAGES, ResNet50, synthetic_imagenet
 class ResNetTrainer:
     def __init__(self, batch, device, comm=None, lr=0.1, momentum=0.9, wd=5e-5, seed=0,
                  image_size=224, stages=STAGES, num_classes=1000, overlap=True, data_seed=0,
-                 zero1=None):
+                 zero1=None, optimizer="momentum", lars_eta=0.001):
+        from ..ops import layerwise
+
+        if optimizer not in ("momentum", "lars"):
+            raise ValueError("ResNetTrainer: optimizer must be momentum or lars, got %r"
+                             % (optimizer,))
+        self.optimizer, self.lars_eta = optimizer, layerwise.check_eta(lars_eta)
         self.batch = batch
         self.device = torch.device(device)
         self.comm = comm
@@ -42,6 +53,10 @@ class ResNetTrainer:
         self.lr, self.momentum, self.wd = lr, momentum, wd
         if zero1 is None:
             zero1 = os.environ.get("DTFX_RESNET_ZERO1", "0") == "1"
+        if zero1 and optimizer == "lars":
+            # (also at world 1, where zero1 is a no-op: the combination never starts anywhere)
+            raise ValueError("ResNetTrainer: zero1 does not go with optimizer lars: a shard cuts "
+                             "through tensors, and a tensor's norm would need every shard")
         self.zero1 = bool(zero1) and self.world > 1
         from ..models.resnet import ALIGN
 
@@ -166,7 +181,11 @@ class ResNetTrainer:
         loss, acc = self.model.forward_backward(x, y, on_bucket_ready=self._on_bucket)
         if self.comm_stream is not None:
             torch.cuda.current_stream(self.device).wait_stream(self.comm_stream)
-        self.model.sgd_step(self.lr, self.momentum, self.wd, gscale=1.0 / self.world)
+        if self.optimizer == "lars":
+            self.model.lars_step(self.lr, self.momentum, self.wd, self.lars_eta,
+                                 gscale=1.0 / self.world)
+        else:
+            self.model.sgd_step(self.lr, self.momentum, self.wd, gscale=1.0 / self.world)
         return loss, acc
 
     def step(self, use_graph=False):

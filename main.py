@@ -73,13 +73,16 @@ def main(argv=None):
         from distributedtensorflowexample_amd.train.eval_job import eval_job
 
         return eval_job(FLAGS)
-    # --optimizer lars | lamb / --lars_eta: the mirrored MLP's update only (ops/layerwise.py)
+    # --optimizer lars | lamb / --lars_eta: the mirrored MLP's update, and lars also ResNet-50's
+    # (ops/layerwise.py)
     from distributedtensorflowexample_amd.ops import layerwise
 
+    resnet_lars = (FLAGS.strategy == "mirrored" and FLAGS.model == "resnet50"
+                   and FLAGS.optimizer == "lars")
     try:
         if FLAGS.strategy != "mirrored":
             layerwise.refuse(FLAGS, "--strategy ps_async (--ps_device cpu and gpu)")
-        elif FLAGS.model != "mlp":
+        elif FLAGS.model != "mlp" and not resnet_lars:
             layerwise.refuse(FLAGS, "--model %s" % FLAGS.model)
         elif getattr(FLAGS, "zero1", False):
             layerwise.refuse(FLAGS, "--zero1 (a sharded owner sees a slice of a tensor, not its "
@@ -110,7 +113,7 @@ def main(argv=None):
             check_kind(FLAGS.optimizer)
         except ValueError as e:
             raise SystemExit(str(e))
-        if FLAGS.model != "mlp":
+        if FLAGS.model != "mlp" and not resnet_lars:
             raise SystemExit("--optimizer %s needs --model mlp under --strategy mirrored (or "
                              "--strategy ps_async --ps_device gpu)" % FLAGS.optimizer)
         if getattr(FLAGS, "zero1", False):
